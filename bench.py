@@ -10,7 +10,14 @@ one process per GPU, each compressing its own 1024 boxes (independent AMR
 units, no data-path collective) -> weak scaling; `value` = all ranks' cells /
 the slowest rank's time.
 
-Legs (sub-objects of the same JSON line):
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up,
+times the N headline steps and prints the line: `ms_per_step` is the
+milliseconds one of those N steps took.  `--dump-outputs DIR` also writes
+what the last timed step produced (dump_outputs).  `--full` adds the
+per-kernel stage times and roofline figures of the headline, the legs below
+and the CPU baseline.
+
+Legs (`--full`; sub-objects of the same JSON line):
   inverse  C2's payloads back to cells (rle_decode + inverse transform) and
            the per-box RMSE (calc_rmse_per_box) of the reconstruction
   host     C2 through the host-buffer boundary (wc_forward_host: pinned host
@@ -58,8 +65,16 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", choices=("c2", "c3", "c4", "c5", "f32_64"), default="c2",
                     help="headline workload (default: BASELINE configs[1], C2)")
-    ap.add_argument("--legs", default=",".join(ALL_LEGS),
-                    help="comma list of extra legs (inverse,host,f32_64,c3,c5,c4; opt-in: cli,dropin) or 'none'")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the per-kernel stage timers and roofline figures, the extra "
+                         "legs (--legs) and the CPU baseline; without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last wc_forward produced as DIR/<name>.npy "
+                         "(float32 / float64): every unit's kept count and payload offset, and the decoded "
+                         "payloads of a fixed, seeded sample of units")
+    ap.add_argument("--legs", default=None,
+                    help="--full: comma list of extra legs (inverse,host,f32_64,c3,c5,c4; opt-in: cli,dropin) or "
+                         "'none' (default: the first six)")
     ap.add_argument("--leg-steps", type=int, default=5, help="timed steps of each extra leg")
     ap.add_argument("--hist-quantile", type=float, default=0.7,
                     help="c4 leg: quantile of the opt-in global-threshold mode (NOT the reference rule)")
@@ -88,7 +103,10 @@ def parse(argv=None):
     ap.add_argument("--rehearse", action="store_true",
                     help="multi-rank rehearsal on a one-GPU box: every rank on device 0, gloo instead of RCCL "
                          "(the kernels, shards and reductions of --gpus N; the numbers are not a scaling result)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full and args.legs not in (None, "none", ""):
+        ap.error("--legs needs --full (a plain run measures the headline only)")
+    return args
 
 
 # ---------------------------------------------------------------------------
@@ -320,6 +338,58 @@ def timed(d: Dist, ctx, step, steps, warmup):
     return time.perf_counter() - t0
 
 
+DUMP_SAMPLE_BYTES = 48 << 20  # budget of the sampled payloads' arrays (every dump stays under 64 MB)
+DUMP_SEED = 20240704
+
+
+def dump_outputs(path, d: Dist, b: Batch):
+    """What the last wc_forward of the timed loop left in the caller's buffers,
+    as float32 / float64 .npy files under `path` (rank r > 0: `<name>_rank<r>`):
+      kept, offsets   every unit's kept count and the byte offset of its payload
+                      in the caller's buffer, wc_forward's fixed slots (n and
+                      n + 1 entries; integers, exact in float64)
+      sample_units    indices of a fixed sample of units: a seeded permutation
+                      of the unit indices, taken while the arrays below fit
+                      DUMP_SAMPLE_BYTES (at least one unit)
+      payload_header  the sampled payloads' five int32 header words
+                      (W, H, D, ncoeff, nruns), one row per sampled unit
+      payload_runs, payload_vals
+                      the sampled payloads' (run, value) pairs, concatenated in
+                      sample order: the int32 runs as float64, the fp32 values
+                      as they are
+    The inputs are a function of the workload alone (bench_workloads.py), so
+    two builds given the same arguments dump comparable arrays."""
+    import numpy as np
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    sfx = f"_rank{d.rank}" if d.rank else ""
+    kept = b.kept[:b.n].cpu().numpy().astype(np.int64)
+    offs = b.offsets[:b.n + 1].cpu().numpy().astype(np.int64)
+    order = np.random.default_rng(DUMP_SEED).permutation(b.n)
+    units, hdr, runs, vals, used = [], [], [], [], 0
+    for i in order:
+        nbytes = 20 + 8 * int(kept[i])
+        cost = 12 * int(kept[i]) + 48  # runs as float64 + values as float32, header and index as float64
+        if units and used + cost > DUMP_SAMPLE_BYTES:
+            break
+        raw = b.payload[int(offs[i]):int(offs[i]) + nbytes].cpu().numpy()
+        pairs = raw[20:].view(np.int32).reshape(-1, 2)
+        units.append(int(i))
+        hdr.append(raw[:20].view(np.int32).astype(np.float64))
+        runs.append(pairs[:, 0].astype(np.float64))
+        vals.append(np.ascontiguousarray(pairs[:, 1]).view(np.float32))
+        used += cost
+    arrays = {
+        "kept": kept.astype(np.float64), "offsets": offs.astype(np.float64),
+        "sample_units": np.array(units, np.float64),
+        "payload_header": np.array(hdr, np.float64).reshape(len(units), 5),
+        "payload_runs": np.concatenate(runs) if runs else np.zeros(0, np.float64),
+        "payload_vals": np.concatenate(vals) if vals else np.zeros(0, np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(out / f"{name}{sfx}.npy", a)
+
+
 def stage_times(ctx, step, steps):
     """Per-kernel average launch times (ms) from hipEvents recorded on the
     context stream around each launch, from `steps` more steps."""
@@ -386,19 +456,12 @@ def headline(args, d: Dist, ctx):
     units, span = rank_units(args.workload, d)
     b = Batch(d, units, spec["dtype"], spec["keep"], inverse="inverse" in args.legs_set)
     secs = timed(d, ctx, lambda: b.forward(ctx), args.steps, args.warmup)
-    stages = stage_times(ctx, lambda: b.forward(ctx), args.steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d, b)
     kept = b.kept_total()
     m = d.reduce({"seconds": secs, "kept": kept, "cells": b.ncells, "boxes": b.n,
                   "payload_bytes": 8 * kept + 20 * b.n})
     elapsed = m["seconds"]
-    # roofline of the dominant kernel: its algorithmic bytes (SURVEY §8(d)) per launch / its launch time
-    own = {"transform": b.s_in * b.ncells, "emit": 8 * kept + 20 * b.n}
-    dominant = max(stages, key=lambda k: stages[k][0])
-    dom_ms = stages[dominant][0]
-    achieved = own.get(dominant, 0) / (dom_ms * 1e-3) / 1e9
-    path_ms = sum(v[0] * v[1] for v in stages.values())
-    path_bytes = alg_bytes_forward(b.s_in, b.ncells, kept, b.n)
-    traffic, tmeta = pmc_traffic(args.pmc, args.workload, spec["dtype"], dominant)
     ms_step = elapsed / args.steps * 1e3
     out = {
         "metric": f"{'fp64' if spec['dtype'] == 'f64' else 'fp32'} cells/s, fwd transform+threshold+pack, "
@@ -422,6 +485,21 @@ def headline(args, d: Dist, ctx):
         "compressed_GBps": m["cells"] * b.s_in * args.steps / elapsed / 1e9,
         "kept_fraction": m["kept"] / max(m["cells"], 1),
         "payload_bytes_per_step": int(m["payload_bytes"]),
+    }
+    if not args.full:
+        return out, b
+    # --full: the per-kernel launch times (args.steps more steps with events
+    # around each launch) and the roofline figures that need them
+    stages = stage_times(ctx, lambda: b.forward(ctx), args.steps)
+    # roofline of the dominant kernel: its algorithmic bytes (SURVEY §8(d)) per launch / its launch time
+    own = {"transform": b.s_in * b.ncells, "emit": 8 * kept + 20 * b.n}
+    dominant = max(stages, key=lambda k: stages[k][0])
+    dom_ms = stages[dominant][0]
+    achieved = own.get(dominant, 0) / (dom_ms * 1e-3) / 1e9
+    path_ms = sum(v[0] * v[1] for v in stages.values())
+    path_bytes = alg_bytes_forward(b.s_in, b.ncells, kept, b.n)
+    traffic, tmeta = pmc_traffic(args.pmc, args.workload, spec["dtype"], dominant)
+    out.update({
         "stage_ms_per_launch": {k: round(v[0], 4) for k, v in stages.items()},
         "roofline": {
             "bound": "hbm", "kernel": dominant,
@@ -437,7 +515,7 @@ def headline(args, d: Dist, ctx):
                           "bytes_per_step": path_bytes, "kernel_ms_per_step": path_ms,
                           "note": "algorithmic bytes / driver-clock ms_per_step (launch gaps included)",
                           **path_traffic(args.pmc, args.workload, spec["dtype"], FWD_STAGES, path_bytes)},
-    }
+    })
     return out, b
 
 
@@ -903,7 +981,11 @@ def plumbing_run(args, d: Dist):
 def main():
     args = parse()
     import wcamd  # noqa: F401  (registers the package as wavelet_compression_amd; no GPU call)
-    args.legs_set = set() if args.legs in ("none", "") else set(args.legs.split(","))
+    # the extra legs, the CPU baseline and the per-kernel figures run under --full only
+    if not args.full or args.legs in ("none", ""):
+        args.legs_set = set()
+    else:
+        args.legs_set = set(ALL_LEGS if args.legs is None else args.legs.split(","))
     if (args.gpus > 1 or args.force_dist) and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
     d = Dist(args.plumbing, args.rehearse, args.dist_timeout, args.force_dist)
@@ -924,7 +1006,7 @@ def main():
     if "host" in args.legs_set and d.world == 1:
         out["host"] = host_leg(args, d, ctx, b)
     out["cpu_baseline"] = None
-    if d.rank == 0 and d.world == 1 and not args.no_cpu_baseline:
+    if args.full and d.rank == 0 and d.world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, b, b.rmse)
     ctx.close()
     del b

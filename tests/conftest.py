@@ -24,6 +24,18 @@ def oracle():
 
 
 @pytest.fixture(scope="session")
+def ref_tests(tmp_path_factory):
+    """A directory holding the reference's fixtures plt00074 and plt00075,
+    rebuilt in place of a checkout of the reference and verified against its
+    recorded hashes before any test reads them."""
+    from ref_plotfiles import check_ref_plotfiles, write_ref_plotfiles
+    dst = tmp_path_factory.mktemp("ref_tests")
+    write_ref_plotfiles(dst)
+    check_ref_plotfiles(dst)
+    return dst
+
+
+@pytest.fixture(scope="session")
 def wc():
     import wcamd
     wcamd.capi.load_library()

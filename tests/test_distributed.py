@@ -258,7 +258,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
     root = Path(__file__).resolve().parent.parent
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--rehearse", "--steps", "2",
-                        "--warmup", "1", "--leg-steps", "1", "--legs", "c5", "--no-cpu-baseline"], env=env,
+                        "--warmup", "1", "--full", "--leg-steps", "1", "--legs", "c5", "--no-cpu-baseline"], env=env,
                        capture_output=True, text=True, timeout=240, cwd=tmp_path)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

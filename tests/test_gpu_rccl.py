@@ -61,7 +61,7 @@ def test_rccl_world1_collectives_equal_no_dist_path(tmp_path):
 
 def test_bench_force_dist_runs_rccl_at_world1(tmp_path):
     cmd = [sys.executable, str(ROOT / "bench.py"), "--force-dist", "--steps", "2", "--warmup", "1",
-           "--leg-steps", "1", "--legs", "c4", "--no-cpu-baseline"]
+           "--full", "--leg-steps", "1", "--legs", "c4", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=110, cwd=tmp_path)
     assert r.returncode == 0, r.stderr[-3000:]
     out = _json(r.stdout)

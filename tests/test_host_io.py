@@ -2,46 +2,32 @@
 .raw side files, plotfile reader and writer, the ParmParse-style parameters,
 file selection and the xz thread pool, through tests/cpp/test_host_io.cpp
 (the reference's own readandwrite / argparse / Preprocessing / Writing
-plotfiles tests, restated).  The reference's fixtures tests/plt0007{4,5} are
-read in place when /root/reference is present (this container) and those
-cases skip elsewhere."""
-import filecmp
-import os
+plotfiles tests, restated).  The reference's fixtures tests/plt0007{4,5} come
+from the `ref_tests` fixture (tests/ref_plotfiles.py: rebuilt, then verified
+against the hashes recorded from the reference's own files)."""
 import subprocess
 from pathlib import Path
 
 import numpy as np
-import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
 BIN = ROOT / "tools" / "bin" / "test_host_io"
 CLI = ROOT / "wavelet-compression_amd" / "bin" / "wavelet-compression"
-REF_TESTS = Path("/root/reference/tests")
 
 
-def test_host_io_cpp_cases():
-    args = [str(BIN)] + ([str(REF_TESTS)] if (REF_TESTS / "plt00074" / "Header").exists() else [])
-    r = subprocess.run(args, capture_output=True, text=True, timeout=300)
+def test_host_io_cpp_cases(ref_tests):
+    r = subprocess.run([str(BIN), str(ref_tests)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "checks passed" in r.stdout
 
 
-@pytest.mark.skipif(not (REF_TESTS / "plt00074" / "Header").exists(), reason="reference fixtures not present")
 def test_python_plotfile_writer_matches_reference_fixture(tmp_path):
     """The Python writer (used by the GPU tests to build inputs) reproduces the
-    reference's tests/plt00074 byte for byte (src/writeplotfile.cpp:315-402 data)."""
-    from wavelet_compression_amd import plotfile as pf
-    b1 = np.full((2, 64, 32, 16), np.float32(3902.4), np.float64)
-    b2 = np.full((2, 2, 4, 8), 16.0)
-    lev = [((0, 0, 0), b1), ((16, 32, 64), b2)]
-    for name, t, steps in (("plt00074", 0.2219392, [1200, 1500]), ("plt00075", 0.3874982, [1800, 2000])):
-        pf.write_plotfile(tmp_path / name, ["temp", "pressure"], t, [0.6, 0.5, 0.4, 0.8, 0.9, 1.0], 2,
-                          (256, 512, 256), steps, [lev, lev])
-        ref = REF_TESTS / name
-        for root, _, files in os.walk(ref):
-            for f in files:
-                a = Path(root) / f
-                assert filecmp.cmp(a, tmp_path / name / a.relative_to(ref), shallow=False), a
+    reference's tests/plt00074 and tests/plt00075 byte for byte (src/writeplotfile.cpp:315-402
+    data): every file has the size and SHA-256 of the reference's, none missing or extra."""
+    from ref_plotfiles import check_ref_plotfiles, write_ref_plotfiles
+    write_ref_plotfiles(tmp_path)
+    check_ref_plotfiles(tmp_path)
 
 
 def test_cli_without_mode_reports_error():

@@ -1,19 +1,13 @@
 """Plotfile reading against the reference's own fixtures.
 
-The reference's tests/plt0007{4,5} are read IN PLACE from /root/reference when
-that directory exists (this container); they are not copied into the repo
-(see DESIGN.md "Oracle and fixtures").  Expectations restate the reference's
+The reference's tests/plt0007{4,5} are rebuilt by the `ref_tests` fixture and
+verified byte for byte against the hashes recorded from the reference's own
+files (tests/ref_plotfiles.py).  Expectations restate the reference's
 Preprocessing test (src/preprocess.cpp:311-377) and String cleaning test
 (src/argparse.cpp:181-187)."""
 import os
-from pathlib import Path
 
 import numpy as np
-import pytest
-
-REF_TESTS = Path("/root/reference/tests")
-needs_ref = pytest.mark.skipif(not (REF_TESTS / "plt00074" / "Header").exists(),
-                               reason="reference fixtures not present on this host")
 
 
 def test_clean_string(wc):
@@ -24,10 +18,9 @@ def test_clean_string(wc):
     assert pf.format_levels(1, 3) == [1, 2, 3]
 
 
-@needs_ref
-def test_preprocessing_expectations(wc):
+def test_preprocessing_expectations(wc, ref_tests):
     from wavelet_compression_amd import plotfile as pf
-    files = [str(REF_TESTS / "plt00074"), str(REF_TESTS / "plt00075")]
+    files = [str(ref_tests / "plt00074"), str(ref_tests / "plt00075")]
     d = pf.preprocess_data(files, ["temp", "pressure"], [0, 1])
     b1 = d.boxes[0][1][0][0].astype(np.float32)   # time 0, level 1, box 0, comp 0
     b2 = d.boxes[1][0][1][1].astype(np.float32)   # time 1, level 0, box 1, comp 1
@@ -45,9 +38,12 @@ def test_preprocessing_expectations(wc):
     assert h0.domain_dims == (256, 512, 256)
 
 
-@needs_ref
-def test_format_files(wc, tmp_path):
+def test_format_files(wc, ref_tests, monkeypatch):
     from wavelet_compression_amd import plotfile as pf
-    files = pf.format_files(str(REF_TESTS), "plt00074", "plt00075")
+    # format_files takes the digits of the WHOLE path (reference quirk,
+    # src/argparse.cpp:146): a data directory given relative to the working
+    # directory, as the reference's own tests give it, has none wherever it lies
+    monkeypatch.chdir(ref_tests)
+    files = pf.format_files(".", "plt00074", "plt00075")
     assert [os.path.basename(f) for f in files] == ["plt00074", "plt00075"]
-    assert [os.path.basename(f) for f in pf.format_files(str(REF_TESTS), "plt00075", "plt00075")] == ["plt00075"]
+    assert [os.path.basename(f) for f in pf.format_files(".", "plt00075", "plt00075")] == ["plt00075"]

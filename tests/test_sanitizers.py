@@ -20,7 +20,6 @@ import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "wavelet-compression_amd" / "csrc"
-REF_TESTS = Path("/root/reference/tests")
 SANS = ("asan", "tsan")
 
 
@@ -47,10 +46,8 @@ def check_clean(r, what):
 
 
 @pytest.mark.parametrize("san", SANS)
-def test_host_io_under_sanitizer(san_bins, san, tmp_path):
-    args = [str(san_bins[san] / "test_host_io")]
-    if (REF_TESTS / "plt00074" / "Header").exists():
-        args.append(str(REF_TESTS))
+def test_host_io_under_sanitizer(san_bins, san, tmp_path, ref_tests):
+    args = [str(san_bins[san] / "test_host_io"), str(ref_tests)]
     r = subprocess.run(args, capture_output=True, text=True, timeout=600, env=san_env(tmp_path))
     check_clean(r, f"{san} test_host_io")
     assert r.returncode == 0 and "checks passed" in r.stdout, r.stdout + r.stderr

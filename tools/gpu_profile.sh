@@ -35,6 +35,8 @@ for w in "${wls[@]}"; do
 done
 steps+=("bench:500:python bench.py --pmc gpurun_out/pmc > gpurun_out/bench_line.txt")
 steps+=("kt_bench:300:rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_bench -o bench -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline --pmc gpurun_out/pmc")
+# both bench steps report every leg and the per-kernel figures: bench.py --full
+steps=("${steps[@]//python bench.py /python bench.py --full }")
 [ "${DROPIN:-0}" = 1 ] && steps+=("dropin:600:tools/bin/dropin_bench /tmp/wcamd_dropin_\$\$ 4 0.999 > gpurun_out/dropin.json")
 [ "${CLI:-0}" = 1 ] && steps+=("cli:600:python tools/bench_cli.py --scale 1.0 --ncomp 4 --out gpurun_out/cli_e2e.json")
 [ "${GPUTEST:-0}" = 1 ] && steps+=("gputest:500:python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread")
