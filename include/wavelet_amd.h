@@ -150,6 +150,13 @@ int wc_synchronize(wc_ctx* ctx);  /* also reports (and clears) kernel-side error
  *   (MADV_HUGEPAGE) on the 2-MiB-aligned interior of those spans first.  Off
  *   by default: the advice splits the caller's mappings and changes their
  *   huge-page policy for the life of the mapping (the caller owns its memory).
+ * WC_OPT_TOL_SOLO_TILES (default 64): the RMSE-tolerance mode (wc_forward_tol)
+ *   bins a unit of up to this many flat tiles (4096 coefficients each) in ONE
+ *   workgroup (LDS bins only); a larger unit is split over several workgroups
+ *   that add their bins to 16 KB of global bins of the unit.  Same thresholds
+ *   and bytes either way; 1 splits every unit of two or more tiles (tests).
+ *   From 63 up (the default included) the global bins take at most 1/64 of
+ *   the split units' coefficient scratch.
  */
 #define WC_OPT_SPARSE 12
 #define WC_OPT_ORDERED 13
@@ -167,6 +174,7 @@ int wc_synchronize(wc_ctx* ctx);  /* also reports (and clears) kernel-side error
  * two-kernel forward in every measured shape) */
 #define WC_OPT_HOST_THREADS 27
 #define WC_OPT_HOST_THP 28
+#define WC_OPT_TOL_SOLO_TILES 30
 int wc_set_option(wc_ctx* ctx, int option, int64_t value);
 int wc_get_option(const wc_ctx* ctx, int option, int64_t* value);
 
@@ -237,6 +245,65 @@ int wc_forward_stage(wc_ctx* ctx, const void* d_cells, int dtype, const wc_unit*
 int wc_hist_threshold(const uint64_t* hist, double quantile, float* thresh, uint64_t* retained);
 int wc_forward_emit(wc_ctx* ctx, const wc_unit* units, int n, double keep, const float* thresh,
                     uint8_t* d_payload, uint64_t payload_capacity, uint64_t* d_offsets, uint32_t* d_kept);
+
+/* Opt-in RMSE-tolerance mode (NOT the reference's rule): the caller states the
+ * tolerated RMSE of each unit and the library finds the unit's threshold.  The
+ * reference's only quality control is `keep` (threshold = the box's own max *
+ * (1 - keep)), so the error of a box follows from its largest coefficient and
+ * its -estimate mode exists to guess `keep` by trial.  Payload format and
+ * decoder unchanged; only the threshold differs.
+ *
+ * With W, H and D all even the one-level transform (avg = (a+b)/2, diff =
+ * (a-b)/2 per axis) is orthogonal and every basis vector has squared norm 8:
+ * dropping the coefficient set S costs SSE = 8 * sum_S c^2, RMSE^2 = SSE / N.
+ * A unit with an odd dimension has no such bound (the reference's inverse does
+ * not restore the trailing plane of an odd axis) and is rejected.
+ *
+ * The selection rule, on one unit's N = W*H*D coefficients and its tolerance
+ * tol (a double >= 0, +inf allowed; NaN or negative: WC_ERR_INVALID):
+ *   cnt[b]  = coefficients with fp32 bits of |c| >> WC_HIST_SHIFT == b (the
+ *             WC_HIST_BINS bins of the global-threshold mode; NaN not counted)
+ *   hi_b    = (double) the float with bits (b + 1) << 19 for b < 0xFEF, +inf
+ *             from there on: every |c| of bin b is < hi_b
+ *   budget  = (tol * tol) * (double)N
+ *   S = 0; for b = 0, 1, ... over the non-empty bins:
+ *       t = S + (double)cnt[b] * (8.0 * (hi_b * hi_b));
+ *       if !(t <= budget) stop: b* = b;  else S = t      (no stop: b* = 4096)
+ *   thresh  = 0.0f if b* == 0 (every non-zero coefficient kept), FLT_MAX if
+ *             b* >= 0xFF0 (only +-inf kept), else the float with bits
+ *             (b* << 19) - 1: the emit's strict |c| > thresh keeps exactly the
+ *             bins >= b*
+ *   bound   = sqrt(S / N) (0 when N == 0): the guaranteed model RMSE of the
+ *             choice, bound <= tol
+ * in IEEE double with separately rounded multiplies and adds.  Only integer
+ * counts enter: the result is the same bits on the host and the device and in
+ * every run.  Conservative by less than one bin step (upper bin edges
+ * overestimate the dropped energy by at most (17/16)^2).  The actual RMSE adds
+ * the fp32 rounding of the round trip to the model's.
+ *
+ *   wc_tol_threshold: host-only; the rule on one unit's counts.
+ *   wc_forward_tol: wc_forward with per-unit tolerances in place of keep.
+ *     tol: n doubles on the HOST, consumed before the call returns.  d_thresh
+ *     (n floats) and d_bound (n doubles): device, nullable.  The coefficients
+ *     are staged densely (the threshold is not known when the transform runs)
+ *     and read once more for the bins.  A unit with cells and an odd W, H or D:
+ *     WC_ERR_INVALID, nothing launched.  A unit without cells keeps nothing.
+ *   wc_forward_emit_tol: the staged form, after wc_forward_stage(..., NULL);
+ *     may be repeated with other tolerances on the same staged batch.
+ *   wc_forward_tol_host: host buffers; payloads packed as wc_forward_host;
+ *     thresh, bound, rmse (n each, host, nullable); rmse = the ACTUAL RMSE of
+ *     each unit's round trip, taken on the device (wc_inverse_rmse).  The unit
+ *     runs (WC_OPT_HOST_CHUNK) go one after another. */
+int wc_tol_threshold(const uint64_t* counts, uint64_t ncoeff, double tol, float* thresh, double* bound);
+int wc_forward_tol(wc_ctx* ctx, const void* d_cells, int dtype, const wc_unit* units, int n, const double* tol,
+                   uint8_t* d_payload, uint64_t payload_capacity, uint64_t* d_offsets, uint32_t* d_kept,
+                   float* d_thresh, double* d_bound);
+int wc_forward_emit_tol(wc_ctx* ctx, const wc_unit* units, int n, const double* tol, uint8_t* d_payload,
+                        uint64_t payload_capacity, uint64_t* d_offsets, uint32_t* d_kept, float* d_thresh,
+                        double* d_bound);
+int wc_forward_tol_host(wc_ctx* ctx, const void* cells, int dtype, const wc_unit* units, int n, const double* tol,
+                        uint8_t* payload, uint64_t payload_capacity, uint64_t* offsets, uint32_t* kept,
+                        float* thresh, double* bound, double* rmse);
 
 /* Transform only: cells -> flat fp32 coefficients (x-slowest order), written
  * at the same element offsets as the cells (d_flat has the cell buffer's extent). */
@@ -330,7 +397,8 @@ int wc_decompose_host(wc_ctx* ctx, const void* cells, int dtype, const wc_unit* 
 #define WC_STAGE_HIST 5       /* histogram pass of generic units (wc_forward_stage with d_hist; the fast
                                  units' bins are counted inside the transform stage) */
 #define WC_STAGE_PAIRS 6      /* header check + pair counts of wc_inverse_rows with a caller row index */
-#define WC_NUM_STAGES 7
+#define WC_STAGE_TOL 7        /* per-unit bins + threshold pick of the RMSE-tolerance mode (wc_forward_tol) */
+#define WC_NUM_STAGES 8
 int wc_profile_enable(wc_ctx* ctx, int on);
 int wc_profile_read(wc_ctx* ctx, double* total_ms, uint32_t* launches, int nstages);
 

@@ -22,6 +22,13 @@ struct Config {
     // for the extreme variant) selects the xz preset of -c; default 6, the
     // reference's (src/compressor.cpp:261).  -1: not given ($WCAMD_XZ_PRESET or 6).
     int xz_preset = -1;
+    // Not a reference parameter: `rmse=T` (one value, or one per entry of
+    // components=) makes -c and -estimate threshold every box so that its RMSE
+    // stays within T (wc_forward_tol_host; boxes need even dimensions) instead
+    // of by `keep`, which is then ignored.  Values >= 0, "inf" allowed.  Empty:
+    // not given.  rmse_error: given but unusable (the run stops before any work).
+    std::vector<double> rmse;
+    bool rmse_error = false;
 };
 
 // Stand-in for amrex::Initialize's ParmParse setup: parse `name=value ...`

@@ -30,6 +30,7 @@ EXPORTED = (
     "wc_decompose_host", "wc_device_count", "wc_forward_stage", "wc_hist_threshold",
     "wc_forward_emit", "wc_inverse_rmse", "wc_get_option", "wc_rowindex_bytes", "wc_forward_rows",
     "wc_inverse_rows", "wc_forward_host_units", "wc_round_trip_host",
+    "wc_tol_threshold", "wc_forward_tol", "wc_forward_emit_tol", "wc_forward_tol_host",
 )
 WC_OPT_SPARSE = 12   # sparse coefficient staging in the forward (default 1)
 WC_OPT_ORDERED = 13  # look-back tile index from the launch order (1, default) or per-unit tickets (0)
@@ -45,9 +46,10 @@ WC_OPT_RIX_XCD = 22  # row-indexed inverse tiles dealt to XCDs in contiguous run
 WC_OPT_INV_GROUPS = 23  # row-indexed inverse in N unit groups, row index of g+1 beside K6r of g (default 1)
 WC_OPT_HOST_THREADS = 27  # _host calls: threads that fault in a copy's host destination first (0 = off)
 WC_OPT_HOST_THP = 28  # _host calls: advise huge pages on those destinations (default 0)
+WC_OPT_TOL_SOLO_TILES = 30  # RMSE-tolerance mode: flat tiles a unit may have and still be binned by one workgroup (default 64)
 
 # Stage ids of wc_profile_read (include/wavelet_amd.h WC_STAGE_*).
-STAGES = ("transform", "emit", "decode", "inverse", "rmse", "hist", "pairs")
+STAGES = ("transform", "emit", "decode", "inverse", "rmse", "hist", "pairs", "tol")
 
 
 class WcUnit(ctypes.Structure):
@@ -113,6 +115,11 @@ def load_library() -> ctypes.CDLL:
         "wc_inverse_rows": (i32, [vp, vp, vp, up, i32, vp, u64, vp, i32, vp, vp]),
         "wc_forward_host_units": (i32, [vp, ctypes.POINTER(vp), i32, up, i32, ctypes.c_double, vp, u64, vp, vp]),
         "wc_round_trip_host": (i32, [vp, vp, i32, up, i32, ctypes.c_double, vp, u64, vp, vp, vp]),
+        "wc_tol_threshold": (i32, [vp, u64, ctypes.c_double, ctypes.POINTER(ctypes.c_float),
+                                   ctypes.POINTER(ctypes.c_double)]),
+        "wc_forward_tol": (i32, [vp, vp, i32, up, i32, vp, vp, u64, vp, vp, vp, vp]),
+        "wc_forward_emit_tol": (i32, [vp, up, i32, vp, vp, u64, vp, vp, vp, vp]),
+        "wc_forward_tol_host": (i32, [vp, vp, i32, up, i32, vp, vp, u64, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -269,6 +276,25 @@ class Context:
         self._check(self._L.wc_forward_emit(self._h, units, n, float(keep), t, ctypes.c_void_p(d_payload),
                                             capacity, ctypes.c_void_p(d_offsets), ctypes.c_void_p(d_kept)))
 
+    def forward_tol(self, d_cells: int, dtype: int, units, n: int, tol, d_payload: int, capacity: int,
+                    d_offsets: int, d_kept: int, d_thresh: int | None = None, d_bound: int | None = None):
+        """wc_forward with per-unit RMSE tolerances (n host doubles) in place of
+        keep; d_thresh (n floats) / d_bound (n doubles): optional device outputs."""
+        t = _tol_array(tol, n)
+        self._check(self._L.wc_forward_tol(self._h, ctypes.c_void_p(d_cells), dtype, units, n, t.ctypes.data,
+                                           ctypes.c_void_p(d_payload), capacity, ctypes.c_void_p(d_offsets),
+                                           ctypes.c_void_p(d_kept), ctypes.c_void_p(d_thresh or 0),
+                                           ctypes.c_void_p(d_bound or 0)))
+
+    def forward_emit_tol(self, units, n: int, tol, d_payload: int, capacity: int, d_offsets: int, d_kept: int,
+                         d_thresh: int | None = None, d_bound: int | None = None):
+        """The staged form of forward_tol, after forward_stage(..., None); may be
+        repeated with other tolerances on the same staged batch."""
+        t = _tol_array(tol, n)
+        self._check(self._L.wc_forward_emit_tol(self._h, units, n, t.ctypes.data, ctypes.c_void_p(d_payload),
+                                                capacity, ctypes.c_void_p(d_offsets), ctypes.c_void_p(d_kept),
+                                                ctypes.c_void_p(d_thresh or 0), ctypes.c_void_p(d_bound or 0)))
+
     def decompose(self, d_cells: int, dtype: int, units, n: int, d_flat: int):
         self._check(self._L.wc_decompose(self._h, ctypes.c_void_p(d_cells), dtype, units, n,
                                          ctypes.c_void_p(d_flat)))
@@ -335,6 +361,27 @@ class Context:
                                                payload.ctypes.data, cap, offsets.ctypes.data, kept.ctypes.data,
                                                rmse.ctypes.data))
         return payload, offsets, kept[:n], rmse[:n]
+
+    def forward_tol_host(self, cells: np.ndarray, units, n: int, tol):
+        """wc_forward_tol_host: per-unit RMSE tolerances in place of keep ->
+        (payload, offsets, kept, thresh, bound, rmse); rmse is the actual RMSE of
+        each unit's round trip, taken on the device."""
+        c = np.ascontiguousarray(cells)
+        if c.dtype not in (np.float32, np.float64):
+            raise TypeError("cells must be float32 or float64")
+        dtype = WC_F64 if c.dtype == np.float64 else WC_F32
+        t = _tol_array(tol, n)
+        cap = payload_bound(units, n)
+        payload = np.empty(cap, np.uint8)
+        offsets = np.zeros(n + 1, np.uint64)
+        kept = np.zeros(max(n, 1), np.uint32)
+        thresh = np.zeros(max(n, 1), np.float32)
+        bound = np.zeros(max(n, 1), np.float64)
+        rmse = np.zeros(max(n, 1), np.float64)
+        self._check(self._L.wc_forward_tol_host(self._h, c.ctypes.data, dtype, units, n, t.ctypes.data,
+                                                payload.ctypes.data, cap, offsets.ctypes.data, kept.ctypes.data,
+                                                thresh.ctypes.data, bound.ctypes.data, rmse.ctypes.data))
+        return payload, offsets, kept[:n], thresh[:n], bound[:n], rmse[:n]
 
     def forward_host_units(self, boxes, units, n: int, keep: float):
         """wc_forward_host_units: unit u's cells from boxes[u] (its own host
@@ -403,6 +450,29 @@ def hist_threshold(hist: np.ndarray, quantile: float):
     if rc:
         raise WaveletError(rc, "wc_hist_threshold: invalid argument")
     return float(t.value), int(r.value)
+
+
+def _tol_array(tol, n: int) -> np.ndarray:
+    """Per-unit tolerances as n contiguous doubles (one value: the same for every unit)."""
+    t = np.ascontiguousarray(np.broadcast_to(np.asarray(tol, np.float64), (n,)) if np.ndim(tol) == 0 else tol,
+                             dtype=np.float64)
+    if t.shape != (n,):
+        raise ValueError(f"tol: one value or {n} values")
+    return t
+
+
+def tol_threshold(counts: np.ndarray, ncoeff: int, tol: float):
+    """wc_tol_threshold (host only): (fp32 threshold, model RMSE bound) of the
+    RMSE-tolerance rule on one unit's WC_HIST_BINS uint64 bin counts."""
+    h = np.ascontiguousarray(counts, dtype=np.uint64)
+    if h.size != HIST_BINS:
+        raise ValueError(f"histogram must have {HIST_BINS} bins")
+    t = ctypes.c_float()
+    b = ctypes.c_double()
+    rc = load_library().wc_tol_threshold(h.ctypes.data, int(ncoeff), float(tol), ctypes.byref(t), ctypes.byref(b))
+    if rc:
+        raise WaveletError(rc, "wc_tol_threshold: invalid argument")
+    return float(t.value), float(b.value)
 
 
 def unit_payload(payload: np.ndarray, offsets: np.ndarray, kept: np.ndarray, u: int) -> bytes:

@@ -7,6 +7,8 @@
 // missing parameter is logged and the run continues (src/argparse.cpp:17-68).
 #include <algorithm>
 #include <cctype>
+#include <cmath>
+#include <cstdlib>
 #include <filesystem>
 #include <limits>
 #include <map>
@@ -100,7 +102,28 @@ Config parse_config_compress() {
     if (!query("minlevel", cfg.min_level)) log_error("Missing minlevel!");
     if (!query("maxlevel", cfg.max_level)) log_error("Missing maxlevel!");
     if (!queryarr("components", cfg.components)) log_error("Missing component list!");
-    if (!query("keep", cfg.keep)) log_error("Missing 'keep' parameter!");
+    std::vector<std::string> tols;  // optional, not a reference parameter
+    const bool has_rmse = queryarr("rmse", tols);
+    if (!query("keep", cfg.keep) && !has_rmse) log_error("Missing 'keep' parameter!");
+    if (has_rmse) {
+        for (const std::string& t : tols) {
+            // a definition's values run up to the next `name=`: a mode flag after them is not one
+            if (t == "-c" || t == "-d" || t == "-estimate") continue;
+            char* end = nullptr;
+            const double v = std::strtod(t.c_str(), &end);
+            if (end == t.c_str() || *end != 0 || !(v >= 0.0)) {
+                log_error("Bad rmse (a tolerance >= 0, or inf): " + t);
+                cfg.rmse_error = true;
+            }
+            cfg.rmse.push_back(v);
+        }
+        if (!cfg.rmse_error && cfg.rmse.size() != 1 && cfg.rmse.size() != cfg.components.size()) {
+            log_error("Bad rmse: " + std::to_string(cfg.rmse.size()) + " values for " +
+                      std::to_string(cfg.components.size()) + " components (give one value, or one per component)");
+            cfg.rmse_error = true;
+        }
+        if (cfg.rmse_error) cfg.rmse.clear();
+    }
     if (!query("compresseddir", cfg.compressed_dir)) log_error("Missing compresseddir!");
     std::string preset;  // optional, not a reference parameter: no error when absent
     if (query("xzpreset", preset)) {

@@ -115,6 +115,7 @@ struct RunIndex {
     std::vector<std::string> files;
     std::vector<int> levels;
     std::vector<int> comp_idxs;
+    std::vector<std::string> comp_names;  // the header's names of comp_idxs (header order)
     std::vector<std::vector<std::vector<FabRef>>> fabs;  // [t][lev][box]
     LocDimData locations, dimensions;
     std::vector<std::vector<int>> box_counts;
@@ -136,6 +137,7 @@ RunIndex index_run(const std::vector<std::string>& files, const std::vector<std:
                           "their names exactly in the AMReX Header files.");
                 return r;
             }
+            for (int idx : r.comp_idxs) r.comp_names.push_back(h.names[idx]);
             r.amrexinfo.ref_ratios = h.ref_ratios;
         }
         if (h.dim != 3) log_error("Error: you are using a 3D build to open a " + std::to_string(h.dim) + "D plotfile");
@@ -218,10 +220,25 @@ struct Packed {
     std::vector<double> rmse;  // round trip (estimate): calc_rmse_per_box of every unit
 };
 
+// `rmse=`: the tolerance of each component slot of a box (the units of a box
+// are in header order, the values in the order of components=); empty when the
+// parameter was not given.
+std::vector<double> slot_tolerances(const Config& cfg, const RunIndex& r) {
+    std::vector<double> tol;
+    if (cfg.rmse.empty()) return tol;
+    for (const std::string& name : r.comp_names) {
+        const size_t k = std::find(cfg.components.begin(), cfg.components.end(), name) - cfg.components.begin();
+        tol.push_back(cfg.rmse.size() == 1 ? cfg.rmse[0] : cfg.rmse[std::min(k, cfg.rmse.size() - 1)]);
+    }
+    log_info("rmse= given: every box is thresholded to its RMSE tolerance (not a reference parameter); keep is ignored");
+    return tol;
+}
+
 // The chunk's forward; round_trip: also decode the payloads again and take
 // each unit's RMSE against its cells, on the device (wc_round_trip_host: the
-// reconstruction never comes back to the host).
-Packed forward_chunk(const Chunk& c, double keep, bool round_trip) {
+// reconstruction never comes back to the host).  tol (one value per component
+// slot, or empty): the RMSE-tolerance mode in place of the keep rule.
+Packed forward_chunk(const Chunk& c, double keep, bool round_trip, const std::vector<double>& tol) {
     Packed p;
     const int n = (int)c.units.size();
     const uint64_t cap = wc_payload_bound(c.units.data(), n);
@@ -229,7 +246,15 @@ Packed forward_chunk(const Chunk& c, double keep, bool round_trip) {
     p.offsets.resize(n + 1);
     p.kept.resize(n);
     wc_ctx* ctx = thread_ctx();
-    if (round_trip) {
+    if (!tol.empty()) {
+        std::vector<double> utol(n);
+        for (int u = 0; u < n; ++u) utol[u] = tol[u % tol.size()];
+        if (round_trip) p.rmse.resize(n);
+        check(ctx, wc_forward_tol_host(ctx, c.cells.data(), WC_F64, c.units.data(), n, utol.data(), p.payload.get(),
+                                       cap, p.offsets.data(), p.kept.data(), nullptr, nullptr,
+                                       round_trip ? p.rmse.data() : nullptr),
+              "GPU forward (rmse=)");
+    } else if (round_trip) {
         p.rmse.resize(n);
         check(ctx, wc_round_trip_host(ctx, c.cells.data(), WC_F64, c.units.data(), n, keep, p.payload.get(), cap,
                                       p.offsets.data(), p.kept.data(), p.rmse.data()),
@@ -285,7 +310,7 @@ uint64_t run_cells(const RunIndex& r, size_t nc) {
 // arrive in any order and concurrently, so it does its own locking.
 template <class OnChunk>
 void compress_run(const RunIndex& r, double keep, const std::filesystem::path& dir, OnChunk on_chunk,
-                  const std::vector<int>& devs, bool round_trip = false) {
+                  const std::vector<int>& devs, bool round_trip = false, const std::vector<double>& tol = {}) {
     const size_t nc = r.comp_idxs.size();
     std::vector<Chunk> chunks = plan_chunks(r, nc, chunk_cells(run_cells(r, nc), devs.size()));
     auto jobs_of = [&](const Chunk& c, const Packed& p) {
@@ -306,7 +331,7 @@ void compress_run(const RunIndex& r, double keep, const std::filesystem::path& d
         for (size_t i = next.fetch_add(1); i < chunks.size(); i = next.fetch_add(1)) {
             Chunk& c = chunks[i];
             load_chunk(r, c, threads);
-            auto p = std::make_shared<Packed>(forward_chunk(c, keep, round_trip));
+            auto p = std::make_shared<Packed>(forward_chunk(c, keep, round_trip, tol));
             std::vector<XzJob> jobs = jobs_of(c, *p);
             if (xz_done.valid()) xz_done.get();
             xz_done = std::async(std::launch::async,
@@ -322,6 +347,7 @@ void compress_run(const RunIndex& r, double keep, const std::filesystem::path& d
 }  // namespace
 
 int compress(const Config& cfg) {
+    if (cfg.rmse_error) return 1;
     if (cfg.xz_preset >= 0) set_xz_preset((uint32_t)cfg.xz_preset);
     if (xz_preset() != 6) log_info("xz preset " + std::to_string(xz_preset() & 0xff) +
                                    ((xz_preset() & 0x80000000u) ? "e" : "") + " (the reference's is 6)");
@@ -348,7 +374,7 @@ int compress(const Config& cfg) {
     log_info("Successfully processed data in " + fmt_double(since(t0)) + " seconds. Beginning compression...");
     const auto t1 = Clock::now();
     compress_run(r, (double)cfg.keep, std::filesystem::path(cfg.compressed_dir),
-                 [](size_t, const Chunk&, const Packed&) {}, run_devices());
+                 [](size_t, const Chunk&, const Packed&) {}, run_devices(), false, slot_tolerances(cfg, r));
     log_info("Compression completed in " + fmt_double(since(t1)) + " seconds.");
     return 0;
 }
@@ -423,6 +449,7 @@ int decompress(const Config& cfg) {
 }
 
 int estimate(Config& cfg) {
+    if (cfg.rmse_error) return 1;
     const int num_components = (int)cfg.components.size();
     TempDir scratch;
     const std::vector<std::string> files = format_files(cfg.data_dir, cfg.min_time, cfg.min_time);
@@ -461,7 +488,7 @@ int estimate(Config& cfg) {
             maxv[k] = std::max(maxv[k], hi[k]);
         }
         chunk_rmse[ci] = p.rmse;
-    }, run_devices(), /*round_trip=*/true);
+    }, run_devices(), /*round_trip=*/true, slot_tolerances(cfg, r));
     for (const auto& [ci, rm] : chunk_rmse)
         for (size_t u = 0; u < rm.size(); ++u) all_rmses[u % nc].push_back(rm[u]);
     // The reference reads every file back (src/modes.cpp:250-265) and exits on

@@ -5,7 +5,8 @@
 // cached batch plans (wc_plan.cpp), and turns a batch of units into kernel
 // launches.  No CPU fallback exists: every computing entry point launches HIP
 // kernels and fails with WC_ERR_HIP if the device or code object is absent.
-// The _host entry points are in wc_hostpipe.cpp.
+// The _host entry points are in wc_hostpipe.cpp (wc_forward_tol_host and the
+// host-only wc_tol_threshold: wc_tolhost.cpp).
 //
 // Forward path per batch (wc_forward), every unit shape: K1 k_transform{,_fast}
 // -> flat coefficients in HBM scratch (sparse staging: only the flagged
@@ -21,6 +22,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <string>
+#include <vector>
 
 using namespace wc;
 
@@ -59,7 +62,7 @@ int stage_transform(wc_ctx* c, const void* d_cells, int dtype, double keep, bool
 // (gthresh: the global-threshold mode's fp32 threshold, or null).  Uses the
 // unit keys and the zeroed tickets / look-back granules of the per-call state.
 int stage_emit(wc_ctx* c, int n, double keep, const float* gthresh, uint8_t* d_payload, uint64_t* d_offsets,
-               uint32_t* d_kept, uint2* d_rows = nullptr) {
+               uint32_t* d_kept, uint2* d_rows = nullptr, const float* d_uthresh = nullptr) {
     Plan& P = c->plan;
     uint8_t* st = (uint8_t*)c->state.p;
     EmitParams p{};
@@ -79,8 +82,9 @@ int stage_emit(wc_ctx* c, int n, double keep, const float* gthresh, uint8_t* d_p
         p.use_gthresh = 1;
         p.gthresh = *gthresh;
     }
-    p.flags = (c->sparse_staged && !gthresh) ? (const uint8_t*)c->flags.p : nullptr;
+    p.flags = (c->sparse_staged && !gthresh && !d_uthresh) ? (const uint8_t*)c->flags.p : nullptr;
     p.rowinfo = d_rows;
+    p.uthresh = d_uthresh;
     StageTimer t(c, WC_STAGE_EMIT);
     hipError_t e = launch_emit(c->stream, p, (const float*)c->coef.p, P.nedesc_small,
                                (uint32_t)P.edesc.size() - P.nedesc_small);
@@ -92,6 +96,77 @@ int forward_staged(wc_ctx* c, const void* d_cells, int dtype, int n, double keep
                    uint64_t* d_offsets, uint32_t* d_kept, uint2* d_rows = nullptr) {
     int rc = stage_transform(c, d_cells, dtype, keep, c->opt_sparse);
     return rc ? rc : stage_emit(c, n, keep, nullptr, d_payload, d_offsets, d_kept, d_rows);
+}
+
+// RMSE-tolerance mode, between the dense staging and the emit: unit u's
+// threshold (and model bound) from its own magnitude bins (wc_tol.hip).  The
+// tolerances and the solo / split layout of this call go through the context's
+// pinned block (the caller's array is consumed here).  *uthresh: the device
+// thresholds for the emit (d_thresh, or context scratch when that is null).
+int stage_tol(wc_ctx* c, int n, const double* tol, float* d_thresh, double* d_bound, const float** uthresh) {
+    const Plan& P = c->plan;
+    // A unit of more than opt_tol_solo flat tiles is split into runs of `chunk`
+    // tiles, one workgroup each.
+    const uint32_t solo = (uint32_t)c->opt_tol_solo;
+    const uint32_t chunk = std::min<uint32_t>(solo, 8);
+    std::vector<uint32_t> slot(n), split;
+    std::vector<uint2> items;
+    for (int u = 0; u < n; ++u) {
+        const uint32_t nt = P.units[u].nftiles;
+        if (nt <= solo) {
+            slot[u] = 0xffffffffu;
+            continue;
+        }
+        slot[u] = (uint32_t)split.size();
+        split.push_back((uint32_t)u);
+        for (uint32_t t = 0; t < nt; t += chunk) items.push_back(make_uint2((uint32_t)u, t));
+    }
+    const size_t nsplit = split.size(), nitems = items.size();
+    // tol[n] | items[nitems] | slot[n] | split_units[nsplit] (8-B members first) | thresh[n]
+    const size_t o_items = sizeof(double) * n, o_slot = o_items + sizeof(uint2) * nitems, o_split = o_slot + 4ull * n,
+                 in_bytes = o_split + 4 * nsplit, o_thresh = round_up(in_bytes, 8);
+    int rc;
+    hipError_t e;
+    if ((rc = ensure(c, c->tol_in, o_thresh + sizeof(float) * n)) ||
+        (nsplit && (rc = ensure(c, c->tol_bins, sizeof(uint32_t) * WC_HIST_BINS * nsplit))))
+        return rc;
+    if (!c->tol_ev && (e = hipEventCreateWithFlags(&c->tol_ev, hipEventDisableTiming)) != hipSuccess)
+        return hip_fail(c, e, "event");
+    // the previous call's copy out of the pinned block has finished
+    if (c->tol_ev_live && (e = hipEventSynchronize(c->tol_ev)) != hipSuccess) return hip_fail(c, e, "tolerance upload");
+    c->tol_ev_live = false;
+    if (c->tol_pin_bytes < in_bytes) {
+        if (c->tol_pin) (void)hipHostFree(c->tol_pin);
+        c->tol_pin = nullptr;
+        c->tol_pin_bytes = 0;
+        const size_t want = std::max(in_bytes, size_t(4096));
+        if ((e = hipHostMalloc(&c->tol_pin, want, hipHostMallocDefault)) != hipSuccess) {
+            c->tol_pin = nullptr;
+            return fail(c, WC_ERR_NOMEM, std::string("pinned tolerances: ") + hipGetErrorString(e));
+        }
+        c->tol_pin_bytes = want;
+    }
+    uint8_t* pin = (uint8_t*)c->tol_pin;
+    std::memcpy(pin, tol, sizeof(double) * n);
+    if (nitems) std::memcpy(pin + o_items, items.data(), sizeof(uint2) * nitems);
+    std::memcpy(pin + o_slot, slot.data(), 4ull * n);
+    if (nsplit) std::memcpy(pin + o_split, split.data(), 4 * nsplit);
+    uint8_t* d = (uint8_t*)c->tol_in.p;
+    if ((e = hipMemcpyAsync(d, pin, in_bytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
+        (e = hipEventRecord(c->tol_ev, c->stream)) != hipSuccess)
+        return hip_fail(c, e, "tolerance upload");
+    c->tol_ev_live = true;
+    if (nsplit && (e = hipMemsetAsync(c->tol_bins.p, 0, sizeof(uint32_t) * WC_HIST_BINS * nsplit, c->stream)) !=
+                      hipSuccess)
+        return hip_fail(c, e, "memset bins");
+    float* th = d_thresh ? d_thresh : (float*)(d + o_thresh);
+    StageTimer t(c, WC_STAGE_TOL);
+    e = launch_tol(c->stream, (const UnitDev*)P.d_units.p, n, (const uint32_t*)(d + o_slot),
+                   (const uint2*)(d + o_items), (uint32_t)nitems, chunk, (const uint32_t*)(d + o_split),
+                   (uint32_t)nsplit, (const float*)c->coef.p, (uint32_t*)c->tol_bins.p, (const double*)d, th, d_bound);
+    if (e != hipSuccess) return hip_fail(c, e, "tolerance launch");
+    *uthresh = th;
+    return WC_OK;
 }
 
 }  // namespace
@@ -142,7 +217,8 @@ void wc_ctx_destroy(wc_ctx* c) {
                       &c->h_rows,        &c->h_rmse,
                       &c->plan.d_units,  &c->plan.d_xtiles,  &c->plan.d_ftiles,  &c->plan.d_dtiles,
                       &c->plan.d_edesc, &c->plan.d_ixtiles, &c->plan.d_rtiles,
-                      &c->plan.d_rdtiles, &c->rowinfo,    &c->istate,        &c->npairs};
+                      &c->plan.d_rdtiles, &c->rowinfo,    &c->istate,        &c->npairs,
+                      &c->tol_in,        &c->tol_bins,       &c->h_thresh,       &c->h_bound};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (Plan& P : c->plan_cache) free_plan(P);
@@ -153,6 +229,8 @@ void wc_ctx_destroy(wc_ctx* c) {
     if (c->down) (void)hipStreamDestroy(c->down);
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->bounce) (void)hipHostFree(c->bounce);
+    if (c->tol_pin) (void)hipHostFree(c->tol_pin);
+    if (c->tol_ev) (void)hipEventDestroy(c->tol_ev);
     for (hipEvent_t e : c->bev) (void)hipEventDestroy(e);
     for (auto& m : c->marks) {
         c->ev_pool.push_back(m.a);
@@ -236,6 +314,11 @@ int wc_set_option(wc_ctx* c, int option, int64_t value) {
         case WC_OPT_HOST_THP:
             c->opt_host_thp = value != 0;
             return WC_OK;
+        case WC_OPT_TOL_SOLO_TILES:
+            if (value < 1 || value > (int64_t(1) << 19))
+                return fail(c, WC_ERR_INVALID, "WC_OPT_TOL_SOLO_TILES: 1..2^19 flat tiles");
+            c->opt_tol_solo = (int)value;
+            return WC_OK;
         default:
             return fail(c, WC_ERR_INVALID, "unknown option");
     }
@@ -260,6 +343,7 @@ int wc_get_option(const wc_ctx* c, int option, int64_t* value) {
             *value = c->opt_host_threads < 0 ? host_threads_default() : c->opt_host_threads;
             return WC_OK;
         case WC_OPT_HOST_THP: *value = c->opt_host_thp; return WC_OK;
+        case WC_OPT_TOL_SOLO_TILES: *value = c->opt_tol_solo; return WC_OK;
         default: return WC_ERR_INVALID;
     }
 }
@@ -417,6 +501,62 @@ int wc_forward_emit(wc_ctx* c, const wc_unit* units, int n, double keep, const f
     if (e != hipSuccess) return hip_fail(c, e, "memset status");
     if ((rc = stage_emit(c, n, keep, thresh, d_payload, d_offsets, d_kept))) return rc;
     c->staged = true;  // the coefficients are still there: emit again with another threshold
+    return WC_OK;
+}
+
+int wc_forward_tol(wc_ctx* c, const void* d_cells, int dtype, const wc_unit* units, int n, const double* tol,
+                   uint8_t* d_payload, uint64_t cap, uint64_t* d_offsets, uint32_t* d_kept, float* d_thresh,
+                   double* d_bound) {
+    if (!c) return WC_ERR_INVALID;
+    int rc;
+    if ((rc = validate_units(c, units, n))) return rc;
+    if (dtype != WC_F32 && dtype != WC_F64) return fail(c, WC_ERR_INVALID, "dtype");
+    if (n == 0) return WC_OK;
+    if (!d_cells || !d_payload || !d_offsets || !d_kept) return fail(c, WC_ERR_INVALID, "null buffer");
+    if ((rc = validate_tol(c, units, n, tol))) return rc;
+    if (cap < wc_payload_bound(units, n)) return fail(c, WC_ERR_INVALID, "payload_capacity < wc_payload_bound");
+    if ((rc = check_aligned(c, d_cells, "cells")) || (rc = check_aligned(c, d_payload, "payload")) ||
+        (rc = check_aligned(c, d_offsets, "offsets", 8)) || (rc = check_aligned(c, d_kept, "kept", 4)) ||
+        (rc = check_aligned(c, d_thresh, "thresh", 4)) || (rc = check_aligned(c, d_bound, "bound", 8)))
+        return rc;
+    if ((rc = set_device(c)) || (rc = get_plan(c, units, n))) return rc;
+    if ((rc = ensure_scratch(c))) return rc;
+    // dense staging: the threshold is not known when the transform runs
+    const float* uth = nullptr;
+    if ((rc = stage_transform(c, d_cells, dtype, 0.0, false)) || (rc = stage_tol(c, n, tol, d_thresh, d_bound, &uth)))
+        return rc;
+    return stage_emit(c, n, 0.0, nullptr, d_payload, d_offsets, d_kept, nullptr, uth);
+}
+
+int wc_forward_emit_tol(wc_ctx* c, const wc_unit* units, int n, const double* tol, uint8_t* d_payload, uint64_t cap,
+                        uint64_t* d_offsets, uint32_t* d_kept, float* d_thresh, double* d_bound) {
+    if (!c) return WC_ERR_INVALID;
+    int rc;
+    if ((rc = validate_units(c, units, n))) return rc;
+    if (n == 0) return WC_OK;
+    if (!d_payload || !d_offsets || !d_kept) return fail(c, WC_ERR_INVALID, "null buffer");
+    if ((rc = validate_tol(c, units, n, tol))) return rc;
+    if (cap < wc_payload_bound(units, n)) return fail(c, WC_ERR_INVALID, "payload_capacity < wc_payload_bound");
+    if ((rc = check_aligned(c, d_payload, "payload")) || (rc = check_aligned(c, d_offsets, "offsets", 8)) ||
+        (rc = check_aligned(c, d_kept, "kept", 4)) || (rc = check_aligned(c, d_thresh, "thresh", 4)) ||
+        (rc = check_aligned(c, d_bound, "bound", 8)))
+        return rc;
+    const bool staged = c->staged && !c->sparse_staged;  // every coefficient is needed
+    const uint64_t gen = c->plan_gen;
+    if ((rc = set_device(c)) || (rc = get_plan(c, units, n))) return rc;
+    if (!staged || gen != c->plan_gen)
+        return fail(c, WC_ERR_INVALID,
+                    "wc_forward_emit_tol: no staged coefficients for these units (wc_forward_stage)");
+    // tickets and look-back status words are per call (wc_forward_emit)
+    const Plan& P = c->plan;
+    const size_t st_off = 16 + 8ull * n;
+    hipError_t e = hipMemsetAsync((uint8_t*)c->state.p + st_off, 0, P.state_bytes - st_off, c->stream);
+    if (e != hipSuccess) return hip_fail(c, e, "memset status");
+    const float* uth = nullptr;
+    if ((rc = stage_tol(c, n, tol, d_thresh, d_bound, &uth)) ||
+        (rc = stage_emit(c, n, 0.0, nullptr, d_payload, d_offsets, d_kept, nullptr, uth)))
+        return rc;
+    c->staged = true;  // the coefficients are still there: emit again with other tolerances
     return WC_OK;
 }
 

@@ -13,6 +13,9 @@
 //                    own: it calls the device entry points), also built
 //                    against a CPU fake of the HIP runtime for the sanitizer
 //                    tests (tests/cpp/test_hostpipe.cpp)
+//   wc_tolhost.cpp   host side of the RMSE-tolerance mode: the selection rule
+//                    on one unit's counts, the mode's argument checks and
+//                    wc_forward_tol_host (unit runs one after another)
 #pragma once
 
 #include "wavelet_amd.h"
@@ -57,6 +60,8 @@ hipError_t launch_rmse(hipStream_t, const void*, int, const float*, const UnitDe
 hipError_t launch_emit(hipStream_t, const EmitParams&, const float*, uint32_t, uint32_t);
 hipError_t launch_hist(hipStream_t, const UnitDev*, const FTile*, uint32_t, const float*, uint32_t,
                        unsigned long long*, bool);
+hipError_t launch_tol(hipStream_t, const UnitDev*, int, const uint32_t*, const uint2*, uint32_t, uint32_t,
+                      const uint32_t*, uint32_t, const float*, uint32_t*, const double*, float*, double*);
 
 struct DevBuf {
     void* p = nullptr;
@@ -160,6 +165,17 @@ struct wc_ctx {
     // host pages of a copy's destination faulted in ahead of it (wc_hostmem.h)
     int opt_host_threads = -1;    // WC_OPT_HOST_THREADS (-1: not yet resolved from the environment)
     bool opt_host_thp = false;    // WC_OPT_HOST_THP (opt-in: the advice changes the caller's mappings)
+    // RMSE-tolerance mode (wc_forward_tol): the call's tolerances and split
+    // layout go through pinned memory of the context (the caller's array need
+    // not outlive the call); tol_ev orders the next call's rewrite after the copy
+    int opt_tol_solo = 64;        // WC_OPT_TOL_SOLO_TILES
+    void* tol_pin = nullptr;
+    size_t tol_pin_bytes = 0;
+    hipEvent_t tol_ev = nullptr;
+    bool tol_ev_live = false;
+    wc::DevBuf tol_in;            // tol[n] | slot[n] | split_units[nsplit] | items[nitems] | thresh[n]
+    wc::DevBuf tol_bins;          // kHistBins uint32 per split unit (none without split units)
+    wc::DevBuf h_thresh, h_bound; // wc_forward_tol_host: per-unit thresholds and bounds
     std::unique_ptr<wc::HostPool> hpool;
     // uploads from pageable host memory: copied by upool's threads into pinned
     // bounce slots, each slot's copy to the device ordered by an event
@@ -207,6 +223,9 @@ int inverse_stream(wc_ctx* c, int nev);
 
 // wc_hostpipe.cpp
 int host_threads_default();
+
+// wc_tolhost.cpp
+int validate_tol(wc_ctx* c, const wc_unit* units, int n, const double* tol);
 
 // Bracket one launch with events when profiling is on.
 struct StageTimer {

@@ -17,8 +17,11 @@ namespace wc {
 
 // fp32 keep threshold of a unit: the reference rule from the unit's max key
 // (src/compressor.cpp:212-216), or the one global threshold of the opt-in
-// histogram mode (wc_forward_emit with a threshold).
-__device__ __forceinline__ float unit_thresh(const EmitParams& P, unsigned long long key) {
+// histogram mode (wc_forward_emit with a threshold), or unit u's own threshold
+// of the RMSE-tolerance mode (wc_tol.hip wrote it in an earlier launch: one
+// uniform load).
+__device__ __forceinline__ float unit_thresh(const EmitParams& P, unsigned long long key, uint32_t u) {
+    if (P.uthresh) return P.uthresh[u];
     return P.use_gthresh ? P.gthresh : thresh_as_float(key_thresh(key, P.keep));
 }
 
@@ -255,7 +258,7 @@ __device__ __forceinline__ void emit_tile(const EmitParams& P, const Src& src, c
     }
     // the unit key: a finished earlier launch wrote it, one uniform load
     float tf = 0.0f;
-    if constexpr (!kKeyPar) tf = unit_thresh(P, src.key(P, u));
+    if constexpr (!kKeyPar) tf = unit_thresh(P, src.key(P, u), u);
     const uint32_t start = index * kTile;
     const uint32_t len = min(kTile, U.ncells - start);
 
@@ -273,7 +276,7 @@ __device__ __forceinline__ void emit_tile(const EmitParams& P, const Src& src, c
         for (int it = 0; it < 8; ++it)
             q[it] = ((segf >> it) & 1u) ? p4[w * 512 + it * 64 + l] : make_float4(0, 0, 0, 0);
         if constexpr (kKeyPar) {
-            tf = unit_thresh(P, ukey);
+            tf = unit_thresh(P, ukey, u);
             if (!(tf >= 0.0f) && sparse) {  // uniform: the densely re-staged unit, every segment
 #pragma unroll
                 for (int it = 0; it < 8; ++it) q[it] = p4[w * 512 + it * 64 + l];
@@ -286,7 +289,7 @@ __device__ __forceinline__ void emit_tile(const EmitParams& P, const Src& src, c
             q[it] = ((segf >> it) & 1u) && (uint32_t)(w * 2048 + it * 256 + 4 * l) < len ? p4[w * 512 + it * 64 + l]
                                                                                           : make_float4(0, 0, 0, 0);
         if constexpr (kKeyPar) {
-            tf = unit_thresh(P, ukey);
+            tf = unit_thresh(P, ukey, u);
             if (!(tf >= 0.0f) && sparse) {
 #pragma unroll
                 for (int it = 0; it < 8; ++it)

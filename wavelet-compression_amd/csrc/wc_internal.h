@@ -140,6 +140,7 @@ struct EmitParams {
     const uint8_t* flags;          // sparse-staging segment flags (null: every unit dense)
     uint2* rowinfo;                // wc_forward_rows: the payloads' row index out (null: not written);
                                    // unit u's entries at units[u].row_off, units with dmagic != 0
+    const float* uthresh;          // RMSE-tolerance mode: unit u keeps |c| > uthresh[u] (null: the rules above)
 };
 
 constexpr int kSegShift = 4;    // sparse staging: flag index space of 16 coefficients per byte (min segment)
