@@ -37,6 +37,7 @@
  * Payload layout: unit u's serialized bytes, IDENTICAL to the reference's
  * serialize_compressed_wavelet output (src/compressor.cpp:55-80)
  *     int32 W, H, D; int32 ncoeff = W*H*D; int32 nrle; nrle x {int32 run, float32 value}
+ * (ncoeff = -L in the opt-in multi-level mode, wc_forward_levels)
  * start at payload + offsets[u] and are 20 + 8*kept[u] bytes long.  Every
  * offsets[u] is == 4 (mod 8), so each pair is 8-byte aligned.
  *   - wc_forward (device): offsets[u] is unit u's fixed SLOT, the prefix of the
@@ -305,6 +306,85 @@ int wc_forward_tol_host(wc_ctx* ctx, const void* cells, int dtype, const wc_unit
                         uint8_t* payload, uint64_t payload_capacity, uint64_t* offsets, uint32_t* kept,
                         float* thresh, double* bound, double* rmse);
 
+/* Opt-in multi-level transform (NOT the reference's codec, which transforms
+ * each box once): a unit with L >= 2 levels repeats the one-level transform on
+ * the low-pass corner of its coefficient array, the Mallat pyramid in the
+ * unit's own index space.  With one level the 1/8 low-pass octant holds values
+ * of the data's own magnitude, every sensible threshold keeps all of it, and a
+ * unit cannot shrink below about 1/4 of its fp32 cells; further levels shrink
+ * that corner by 8 each.  levels = 1 is the existing codec, byte for byte.
+ *
+ * Definition.  Each unit has L in 1..WC_MAX_LEVELS.  A unit with cells and
+ * L >= 2 needs W, H and D each divisible by 2^L.  A is the unit's flat array
+ * in the x-slowest order (I*H + J)*D + K after the one-level transform
+ * (wc_decompose).  For l = 2..L, with (w, h, d) = (W, H, D) >> (l-1):
+ *   take the sub-box S(x, y, z) = A[(x*H + y)*D + z], x < w, y < h, z < d;
+ *   apply the reference's one-level wavelet_decompose to S as a w x h x d box
+ *     (Z, then Y, then X sweeps; low at m, high at n/2 + m; low = (a + b) * 0.5f,
+ *     high = (a - b) * 0.5f in fp32), giving T in its flat order (I*h + J)*d + K;
+ *   write it back: A[(I*H + J)*D + K] = T[(I*h + J)*d + K].
+ * Threshold, mask, run lengths and serialisation then run on the final A
+ * exactly as for one level: the keep rule's threshold is (1 - keep) * the
+ * signed value at the FIRST flat index of the largest |c| of the final array;
+ * a caller's explicit threshold is the alternative.  The inverse mirrors it:
+ * decode to the dense A; for l = L..2 apply inverse_wavelet_decompose (X, Y, Z;
+ * avg + diff, avg - diff) to the sub-box in place by the same index map; then
+ * the one-level inverse.
+ *
+ * Header.  L = 1 writes the reference's header (ncoeff = W*H*D).  L >= 2
+ * writes ncoeff = -L in that int32 field (W*H*D is redundant with W, H, D), so
+ * every one-level decoder, the reference's included, refuses such a payload
+ * instead of decoding garbage, and a payload or .xz file describes itself.
+ * Slot offsets, pair layout and wc_payload_bound do not change.
+ *
+ * The RMSE-tolerance mode is one-level only: with L >= 2 the basis vectors of
+ * level l have squared norm 8^l, so its rule would need per-level weights.
+ * There is no _tol form of these calls.
+ *
+ *   wc_levels_for: host-only; the largest L <= min(want, WC_MAX_LEVELS) with
+ *     2^L dividing nx, ny and nz; 1 if none does or the box has no cells.
+ *   wc_payload_levels: host-only; L of a payload from its 20-byte header.
+ *     WC_ERR_FORMAT for negative dims, an ncoeff that is neither W*H*D nor
+ *     -2..-WC_MAX_LEVELS, or dims that 2^L does not divide; WC_ERR_INVALID for
+ *     null pointers or len < 20.
+ *   wc_forward_levels: wc_forward with levels[u] per unit (n int32 on the
+ *     HOST, consumed before the call returns) and, as wc_forward_emit, thresh
+ *     = NULL for the keep rule or a host pointer to one fp32 threshold (|c| >
+ *     *thresh kept in every unit).  The coefficients are staged densely.  It
+ *     leaves nothing staged: a following wc_forward_emit / _emit_tol returns
+ *     WC_ERR_INVALID.
+ *   wc_decompose_levels / wc_inverse_flat_levels: the transforms alone
+ *     (wc_decompose / wc_inverse_flat with levels).
+ *   wc_inverse_levels: wc_inverse of such payloads.  Every unit decodes through
+ *     the dense coefficient scratch.  Unit u's header must carry levels[u], else
+ *     WC_ERR_FORMAT at the next wc_synchronize as for other malformed headers;
+ *     nothing past a mismatching header is read and the unit's cells in d_out
+ *     stay untouched (the other units of the batch decode as usual).
+ *   wc_forward_levels_host / wc_inverse_levels_host: host buffers; payloads
+ *     packed as wc_forward_host; the unit runs (WC_OPT_HOST_CHUNK) go one after
+ *     another.  wc_inverse_levels_host takes levels = NULL to read each L from
+ *     its header on the host.
+ * A level outside 1..WC_MAX_LEVELS, or a dimension that 2^L does not divide on
+ * a unit with cells: WC_ERR_INVALID naming the unit, before anything is
+ * launched; outputs stay untouched. */
+#define WC_MAX_LEVELS 4
+int wc_levels_for(int nx, int ny, int nz, int want);
+int wc_payload_levels(const uint8_t* header, size_t len, int* levels);
+int wc_forward_levels(wc_ctx* ctx, const void* d_cells, int dtype, const wc_unit* units, int n,
+                      const int32_t* levels, double keep, const float* thresh, uint8_t* d_payload,
+                      uint64_t payload_capacity, uint64_t* d_offsets, uint32_t* d_kept);
+int wc_decompose_levels(wc_ctx* ctx, const void* d_cells, int dtype, const wc_unit* units, int n,
+                        const int32_t* levels, float* d_flat);
+int wc_inverse_flat_levels(wc_ctx* ctx, const float* d_flat, const wc_unit* units, int n, const int32_t* levels,
+                           float* d_out);
+int wc_inverse_levels(wc_ctx* ctx, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                      const int32_t* levels, float* d_out);
+int wc_forward_levels_host(wc_ctx* ctx, const void* cells, int dtype, const wc_unit* units, int n,
+                           const int32_t* levels, double keep, const float* thresh, uint8_t* payload,
+                           uint64_t payload_capacity, uint64_t* offsets, uint32_t* kept);
+int wc_inverse_levels_host(wc_ctx* ctx, const uint8_t* payload, const uint64_t* offsets, const wc_unit* units, int n,
+                           const int32_t* levels, float* out);
+
 /* Transform only: cells -> flat fp32 coefficients (x-slowest order), written
  * at the same element offsets as the cells (d_flat has the cell buffer's extent). */
 int wc_decompose(wc_ctx* ctx, const void* d_cells, int dtype, const wc_unit* units, int n,
@@ -398,7 +478,9 @@ int wc_decompose_host(wc_ctx* ctx, const void* cells, int dtype, const wc_unit* 
                                  units' bins are counted inside the transform stage) */
 #define WC_STAGE_PAIRS 6      /* header check + pair counts of wc_inverse_rows with a caller row index */
 #define WC_STAGE_TOL 7        /* per-unit bins + threshold pick of the RMSE-tolerance mode (wc_forward_tol) */
-#define WC_NUM_STAGES 8
+#define WC_STAGE_LEVELS 8    /* level passes, key pass and header patch of the multi-level mode (wc_forward_levels,
+                                 wc_inverse_levels) */
+#define WC_NUM_STAGES 9
 int wc_profile_enable(wc_ctx* ctx, int on);
 int wc_profile_read(wc_ctx* ctx, double* total_ms, uint32_t* launches, int nstages);
 

@@ -29,6 +29,14 @@ struct Config {
     // not given.  rmse_error: given but unusable (the run stops before any work).
     std::vector<double> rmse;
     bool rmse_error = false;
+    // Not a reference parameter: `levels=N` (1..4) makes -c and -estimate
+    // transform every box with up to N levels (wc_forward_levels_host; each box
+    // gets wc_levels_for(W, H, D, N), so a box whose dimensions 2^N does not
+    // divide falls back to fewer).  The files then carry their levels in the
+    // header (-d needs no parameter; the reference's decoder refuses them).  Not
+    // together with rmse=.  1: not given.  levels_error: given but unusable.
+    int levels = 1;
+    bool levels_error = false;
 };
 
 // Stand-in for amrex::Initialize's ParmParse setup: parse `name=value ...`

@@ -31,7 +31,10 @@ EXPORTED = (
     "wc_forward_emit", "wc_inverse_rmse", "wc_get_option", "wc_rowindex_bytes", "wc_forward_rows",
     "wc_inverse_rows", "wc_forward_host_units", "wc_round_trip_host",
     "wc_tol_threshold", "wc_forward_tol", "wc_forward_emit_tol", "wc_forward_tol_host",
+    "wc_levels_for", "wc_payload_levels", "wc_forward_levels", "wc_decompose_levels",
+    "wc_inverse_flat_levels", "wc_inverse_levels", "wc_forward_levels_host", "wc_inverse_levels_host",
 )
+WC_MAX_LEVELS = 4  # levels of the opt-in multi-level transform (1 = the reference's codec)
 WC_OPT_SPARSE = 12   # sparse coefficient staging in the forward (default 1)
 WC_OPT_ORDERED = 13  # look-back tile index from the launch order (1, default) or per-unit tickets (0)
 WC_OPT_INVERSE_ROWS = 14  # row-indexed inverse of even-dims units (1, default) or dense decode (0)
@@ -49,7 +52,7 @@ WC_OPT_HOST_THP = 28  # _host calls: advise huge pages on those destinations (de
 WC_OPT_TOL_SOLO_TILES = 30  # RMSE-tolerance mode: flat tiles a unit may have and still be binned by one workgroup (default 64)
 
 # Stage ids of wc_profile_read (include/wavelet_amd.h WC_STAGE_*).
-STAGES = ("transform", "emit", "decode", "inverse", "rmse", "hist", "pairs", "tol")
+STAGES = ("transform", "emit", "decode", "inverse", "rmse", "hist", "pairs", "tol", "levels")
 
 
 class WcUnit(ctypes.Structure):
@@ -120,6 +123,16 @@ def load_library() -> ctypes.CDLL:
         "wc_forward_tol": (i32, [vp, vp, i32, up, i32, vp, vp, u64, vp, vp, vp, vp]),
         "wc_forward_emit_tol": (i32, [vp, up, i32, vp, vp, u64, vp, vp, vp, vp]),
         "wc_forward_tol_host": (i32, [vp, vp, i32, up, i32, vp, vp, u64, vp, vp, vp, vp, vp]),
+        "wc_levels_for": (i32, [i32, i32, i32, i32]),
+        "wc_payload_levels": (i32, [vp, ctypes.c_size_t, ctypes.POINTER(i32)]),
+        "wc_forward_levels": (i32, [vp, vp, i32, up, i32, vp, ctypes.c_double, ctypes.POINTER(ctypes.c_float), vp,
+                                    u64, vp, vp]),
+        "wc_decompose_levels": (i32, [vp, vp, i32, up, i32, vp, vp]),
+        "wc_inverse_flat_levels": (i32, [vp, vp, up, i32, vp, vp]),
+        "wc_inverse_levels": (i32, [vp, vp, vp, up, i32, vp, vp]),
+        "wc_forward_levels_host": (i32, [vp, vp, i32, up, i32, vp, ctypes.c_double, ctypes.POINTER(ctypes.c_float),
+                                         vp, u64, vp, vp]),
+        "wc_inverse_levels_host": (i32, [vp, vp, vp, up, i32, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -295,6 +308,33 @@ class Context:
                                                 capacity, ctypes.c_void_p(d_offsets), ctypes.c_void_p(d_kept),
                                                 ctypes.c_void_p(d_thresh or 0), ctypes.c_void_p(d_bound or 0)))
 
+    def forward_levels(self, d_cells: int, dtype: int, units, n: int, levels, keep: float, thresh: float | None,
+                       d_payload: int, capacity: int, d_offsets: int, d_kept: int):
+        """wc_forward with levels[u] transform levels per unit (n host ints, or one
+        value for all); thresh None: the keep rule on the final array, else one
+        fp32 threshold.  Units with L >= 2 write ncoeff = -L in their headers."""
+        lv = _levels_array(levels, n)
+        t = None if thresh is None else ctypes.byref(ctypes.c_float(thresh))
+        self._check(self._L.wc_forward_levels(self._h, ctypes.c_void_p(d_cells), dtype, units, n, lv.ctypes.data,
+                                              float(keep), t, ctypes.c_void_p(d_payload), capacity,
+                                              ctypes.c_void_p(d_offsets), ctypes.c_void_p(d_kept)))
+
+    def decompose_levels(self, d_cells: int, dtype: int, units, n: int, levels, d_flat: int):
+        lv = _levels_array(levels, n)
+        self._check(self._L.wc_decompose_levels(self._h, ctypes.c_void_p(d_cells), dtype, units, n, lv.ctypes.data,
+                                                ctypes.c_void_p(d_flat)))
+
+    def inverse_flat_levels(self, d_flat: int, units, n: int, levels, d_out: int):
+        lv = _levels_array(levels, n)
+        self._check(self._L.wc_inverse_flat_levels(self._h, ctypes.c_void_p(d_flat), units, n, lv.ctypes.data,
+                                                   ctypes.c_void_p(d_out)))
+
+    def inverse_levels(self, d_payload: int, d_offsets: int, units, n: int, levels, d_out: int):
+        """wc_inverse of multi-level payloads: unit u's header must carry levels[u]."""
+        lv = _levels_array(levels, n)
+        self._check(self._L.wc_inverse_levels(self._h, ctypes.c_void_p(d_payload), ctypes.c_void_p(d_offsets),
+                                              units, n, lv.ctypes.data, ctypes.c_void_p(d_out)))
+
     def decompose(self, d_cells: int, dtype: int, units, n: int, d_flat: int):
         self._check(self._L.wc_decompose(self._h, ctypes.c_void_p(d_cells), dtype, units, n,
                                          ctypes.c_void_p(d_flat)))
@@ -383,6 +423,39 @@ class Context:
                                                 thresh.ctypes.data, bound.ctypes.data, rmse.ctypes.data))
         return payload, offsets, kept[:n], thresh[:n], bound[:n], rmse[:n]
 
+    def forward_levels_host(self, cells: np.ndarray, units, n: int, levels, keep: float,
+                            thresh: float | None = None):
+        """wc_forward_levels_host -> (payload, offsets, kept), packed as forward_host."""
+        c = np.ascontiguousarray(cells)
+        if c.dtype not in (np.float32, np.float64):
+            raise TypeError("cells must be float32 or float64")
+        dtype = WC_F64 if c.dtype == np.float64 else WC_F32
+        lv = _levels_array(levels, n)
+        t = None if thresh is None else ctypes.byref(ctypes.c_float(thresh))
+        cap = payload_bound(units, n)
+        payload = np.empty(cap, np.uint8)
+        offsets = np.zeros(n + 1, np.uint64)
+        kept = np.zeros(max(n, 1), np.uint32)
+        self._check(self._L.wc_forward_levels_host(self._h, c.ctypes.data, dtype, units, n, lv.ctypes.data,
+                                                   float(keep), t, payload.ctypes.data, cap, offsets.ctypes.data,
+                                                   kept.ctypes.data))
+        return payload, offsets, kept[:n]
+
+    def inverse_levels_host(self, payload: np.ndarray, offsets: np.ndarray, units, n: int, extent: int,
+                            levels=None, out=None):
+        """wc_inverse_levels_host -> float32[extent] boxes; levels None: each
+        unit's L is read from its payload header."""
+        p = np.ascontiguousarray(payload, dtype=np.uint8)
+        o = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lv = None if levels is None else _levels_array(levels, n)
+        if out is None:
+            out = np.zeros(max(extent, 1), np.float32)
+        elif out.dtype != np.float32 or out.size < extent or not out.flags.c_contiguous:
+            raise ValueError("out: contiguous float32[>= extent]")
+        self._check(self._L.wc_inverse_levels_host(self._h, p.ctypes.data, o.ctypes.data, units, n,
+                                                   None if lv is None else lv.ctypes.data, out.ctypes.data))
+        return out[:extent]
+
     def forward_host_units(self, boxes, units, n: int, keep: float):
         """wc_forward_host_units: unit u's cells from boxes[u] (its own host
         array, all float32 or all float64) -> (payload, offsets, kept)."""
@@ -459,6 +532,31 @@ def _tol_array(tol, n: int) -> np.ndarray:
     if t.shape != (n,):
         raise ValueError(f"tol: one value or {n} values")
     return t
+
+
+def _levels_array(levels, n: int) -> np.ndarray:
+    """Per-unit levels as n contiguous int32 (one value: the same for every unit)."""
+    lv = np.ascontiguousarray(np.broadcast_to(np.asarray(levels, np.int32), (n,)) if np.ndim(levels) == 0 else levels,
+                              dtype=np.int32)
+    if lv.shape != (n,):
+        raise ValueError(f"levels: one value or {n} values")
+    return lv
+
+
+def levels_for(nx: int, ny: int, nz: int, want: int) -> int:
+    """wc_levels_for (host only): the largest L <= min(want, WC_MAX_LEVELS) with
+    2^L dividing nx, ny and nz; 1 if none does or the box has no cells."""
+    return int(load_library().wc_levels_for(int(nx), int(ny), int(nz), int(want)))
+
+
+def payload_levels(header) -> int:
+    """wc_payload_levels (host only): L of a payload from its first 20 bytes."""
+    h = np.frombuffer(bytes(header), dtype=np.uint8)
+    lv = ctypes.c_int()
+    rc = load_library().wc_payload_levels(h.ctypes.data, h.size, ctypes.byref(lv))
+    if rc:
+        raise WaveletError(rc, "wc_payload_levels: not a payload header")
+    return int(lv.value)
 
 
 def tol_threshold(counts: np.ndarray, ncoeff: int, tol: float):

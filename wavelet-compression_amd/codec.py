@@ -120,27 +120,41 @@ def _pairs_need32(vals: np.ndarray) -> bool:
     return bool(vals.size and np.any(np.abs(vals.astype(np.float64)) > 32767))
 
 
-def compress_payloads(boxes: Sequence[np.ndarray], keep: float, device: int = 0):
+def compress_payloads(boxes: Sequence[np.ndarray], keep: float, device: int = 0, levels: int = 1):
     """Batched forward path: list of Box3D -> list of serialized payload bytes.
 
     One wc_forward_host_units call for the whole list (all units in one launch
     set, each uploaded from its own array: no packing copy on the host, as the
-    C++ mirror's compress())."""
+    C++ mirror's compress()).  levels > 1 (not a reference parameter): the
+    opt-in multi-level transform, each box with the levels its dimensions admit
+    (capi.levels_for); such payloads carry ncoeff = -L in their headers."""
     dims = [_box_dims(b) for b in boxes]
-    units, n, _ = capi.make_units(dims)
     arrs = [np.ascontiguousarray(b, np.float32) for b in boxes]
+    if not 1 <= int(levels) <= capi.WC_MAX_LEVELS:
+        raise ValueError(f"levels: 1..{capi.WC_MAX_LEVELS}, not {levels!r}")
+    if levels > 1:
+        units, n, extent = capi.make_units(dims)
+        cells = np.zeros(max(extent, 1), np.float32)
+        for i, a in enumerate(arrs):
+            cells[units[i].cell_offset:units[i].cell_offset + a.size] = a.ravel()
+        lv = [capi.levels_for(*d, levels) for d in dims]
+        payload, offsets, kept = context(device).forward_levels_host(cells, units, n, lv, keep)
+        return [capi.unit_payload(payload, offsets, kept, i) for i in range(n)]
+    units, n, _ = capi.make_units(dims)
     payload, offsets, kept = context(device).forward_host_units(arrs, units, n, keep)
     return [capi.unit_payload(payload, offsets, kept, i) for i in range(n)]
 
 
 def compress(box: Sequence[np.ndarray], components: Sequence[int], keep: float, time: int,
-             level: int, box_index: int, compressed_dir) -> List[CompressedWavelet]:
+             level: int, box_index: int, compressed_dir, levels: int = 1) -> List[CompressedWavelet]:
     """src/compressor.cpp:192-297.  box[c] is positional; components[c] (an
     AMReX header index) only names the output file.  Writes one .xz file per
-    component and returns the CompressedWavelet structs."""
+    component and returns the CompressedWavelet structs.  levels (not a
+    reference parameter, default 1 = the reference's codec): see
+    compress_payloads; decompress() reads the levels from each file's header."""
     comps = list(components)
     boxes = [box[c] for c in range(len(comps))]
-    payloads = compress_payloads(boxes, keep)
+    payloads = compress_payloads(boxes, keep, levels=levels)
     out = []
     for c, p in enumerate(payloads):
         cw = deserialize_compressed_wavelet(p)
@@ -172,11 +186,15 @@ def read_compressed_payload(file_path) -> bytes:
 
 
 def decompress_payloads(payloads: Sequence[bytes], device: int = 0) -> List[np.ndarray]:
-    """Batched inverse path: serialized payloads -> Box3D arrays (one wc_inverse_host call)."""
+    """Batched inverse path: serialized payloads -> Box3D arrays (one wc_inverse_host
+    call; wc_inverse_levels_host, which reads each payload's levels from its
+    header, when some payload is a multi-level one: ncoeff < 0)."""
     dims = []
+    multi = False
     for p in payloads:
         h = np.frombuffer(p[:20], "<i4")
         dims.append((int(h[0]), int(h[1]), int(h[2])))
+        multi |= int(h[3]) < 0
     units, n, extent = capi.make_units(dims)
     offsets = np.zeros(max(n, 1), np.uint64)
     cur = 4
@@ -187,7 +205,10 @@ def decompress_payloads(payloads: Sequence[bytes], device: int = 0) -> List[np.n
     for i, p in enumerate(payloads):
         o = int(offsets[i])
         buf[o:o + len(p)] = np.frombuffer(p, np.uint8)
-    flat = context(device).inverse_host(buf, offsets, units, n, extent)
+    if multi:
+        flat = context(device).inverse_levels_host(buf, offsets, units, n, extent)
+    else:
+        flat = context(device).inverse_host(buf, offsets, units, n, extent)
     out = []
     for i, (W, H, D) in enumerate(dims):
         o = units[i].cell_offset

@@ -124,6 +124,26 @@ Config parse_config_compress() {
         }
         if (cfg.rmse_error) cfg.rmse.clear();
     }
+    std::vector<std::string> lv;  // optional, not a reference parameter
+    if (queryarr("levels", lv)) {
+        // as for rmse=: a mode flag after the value is not part of it
+        lv.erase(std::remove_if(lv.begin(), lv.end(),
+                                [](const std::string& t) { return t == "-c" || t == "-d" || t == "-estimate"; }),
+                 lv.end());
+        char* end = nullptr;
+        const long v = lv.size() == 1 ? std::strtol(lv[0].c_str(), &end, 10) : 0;
+        if (lv.size() != 1 || end == lv[0].c_str() || *end != 0 || v < 1 || v > 4) {
+            std::string given;
+            for (const std::string& t : lv) given += (given.empty() ? "" : " ") + t;
+            log_error("Bad levels (one integer, 1 to 4): " + given);
+            cfg.levels_error = true;
+        } else if (has_rmse) {
+            log_error("levels= cannot be combined with rmse=: the RMSE-tolerance mode is one-level only");
+            cfg.levels_error = true;
+        } else {
+            cfg.levels = (int)v;
+        }
+    }
     if (!query("compresseddir", cfg.compressed_dir)) log_error("Missing compresseddir!");
     std::string preset;  // optional, not a reference parameter: no error when absent
     if (query("xzpreset", preset)) {

@@ -1,6 +1,7 @@
 // decompressor.cpp — C++ mirror of the reference's decompressor
 // (src/decompressor.cpp:14-255).  xz decode on the host; rle_decode and the
-// inverse transform on the GPU (wc_inverse_host).
+// inverse transform on the GPU (wc_inverse_host; wc_inverse_levels_host for
+// a file of the opt-in multi-level mode, told by its header).
 #include <lzma.h>
 
 #include <cstdint>
@@ -112,6 +113,10 @@ Box3D decompress(std::string file_path, int /*time*/, int /*level*/, int /*compo
     const uint64_t off = 4;
     wc_unit u{0, hdr[0], hdr[1], hdr[2], 0};
     wc_ctx* c = thread_ctx();
-    check(c, wc_inverse_host(c, buf.data(), &off, &u, 1, out.data()), "GPU decompress");
+    // ncoeff < 0: a multi-level payload (not the reference's format; the header carries its levels)
+    if (hdr[3] < 0)
+        check(c, wc_inverse_levels_host(c, buf.data(), &off, &u, 1, nullptr, out.data()), "GPU decompress");
+    else
+        check(c, wc_inverse_host(c, buf.data(), &off, &u, 1, out.data()), "GPU decompress");
     return out;
 }

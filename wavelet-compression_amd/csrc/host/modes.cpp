@@ -237,8 +237,9 @@ std::vector<double> slot_tolerances(const Config& cfg, const RunIndex& r) {
 // The chunk's forward; round_trip: also decode the payloads again and take
 // each unit's RMSE against its cells, on the device (wc_round_trip_host: the
 // reconstruction never comes back to the host).  tol (one value per component
-// slot, or empty): the RMSE-tolerance mode in place of the keep rule.
-Packed forward_chunk(const Chunk& c, double keep, bool round_trip, const std::vector<double>& tol) {
+// slot, or empty): the RMSE-tolerance mode in place of the keep rule.  levels >
+// 1: the multi-level mode, each unit with the levels its dimensions admit.
+Packed forward_chunk(const Chunk& c, double keep, bool round_trip, const std::vector<double>& tol, int levels) {
     Packed p;
     const int n = (int)c.units.size();
     const uint64_t cap = wc_payload_bound(c.units.data(), n);
@@ -254,6 +255,21 @@ Packed forward_chunk(const Chunk& c, double keep, bool round_trip, const std::ve
                                        cap, p.offsets.data(), p.kept.data(), nullptr, nullptr,
                                        round_trip ? p.rmse.data() : nullptr),
               "GPU forward (rmse=)");
+    } else if (levels > 1) {
+        std::vector<int32_t> lv(n);
+        for (int u = 0; u < n; ++u) lv[u] = wc_levels_for(c.units[u].nx, c.units[u].ny, c.units[u].nz, levels);
+        check(ctx, wc_forward_levels_host(ctx, c.cells.data(), WC_F64, c.units.data(), n, lv.data(), keep, nullptr,
+                                          p.payload.get(), cap, p.offsets.data(), p.kept.data()),
+              "GPU forward (levels=)");
+        if (round_trip) {  // decode the same payload bytes again, RMSE against the cells
+            std::vector<float> regen(std::max<uint64_t>(c.ncells, 1));
+            p.rmse.resize(n);
+            check(ctx, wc_inverse_levels_host(ctx, p.payload.get(), p.offsets.data(), c.units.data(), n, lv.data(),
+                                              regen.data()),
+                  "GPU decompress (levels=)");
+            check(ctx, wc_rmse_host(ctx, c.cells.data(), WC_F64, regen.data(), c.units.data(), n, p.rmse.data()),
+                  "GPU RMSE (levels=)");
+        }
     } else if (round_trip) {
         p.rmse.resize(n);
         check(ctx, wc_round_trip_host(ctx, c.cells.data(), WC_F64, c.units.data(), n, keep, p.payload.get(), cap,
@@ -290,7 +306,19 @@ void inverse_batch(const std::vector<std::string>& payloads, const std::vector<w
     std::vector<uint8_t> buf(cur + 8, 0);
     for (size_t i = 0; i < payloads.size(); ++i) std::memcpy(buf.data() + offs[i], payloads[i].data(), payloads[i].size());
     wc_ctx* ctx = thread_ctx();
-    check(ctx, wc_inverse_host(ctx, buf.data(), offs.data(), units.data(), (int)units.size(), out), "GPU decompress");
+    // a multi-level file (levels= at -c) carries ncoeff = -L: such a batch takes the levels from the headers
+    bool multi = false;
+    for (const std::string& p : payloads) {
+        int32_t ncoeff;
+        std::memcpy(&ncoeff, p.data() + 12, 4);
+        multi |= ncoeff < 0;
+    }
+    if (multi)
+        check(ctx, wc_inverse_levels_host(ctx, buf.data(), offs.data(), units.data(), (int)units.size(), nullptr, out),
+              "GPU decompress");
+    else
+        check(ctx, wc_inverse_host(ctx, buf.data(), offs.data(), units.data(), (int)units.size(), out),
+              "GPU decompress");
 }
 
 // The run's cells over all (t, lev, box) and selected components.
@@ -310,7 +338,8 @@ uint64_t run_cells(const RunIndex& r, size_t nc) {
 // arrive in any order and concurrently, so it does its own locking.
 template <class OnChunk>
 void compress_run(const RunIndex& r, double keep, const std::filesystem::path& dir, OnChunk on_chunk,
-                  const std::vector<int>& devs, bool round_trip = false, const std::vector<double>& tol = {}) {
+                  const std::vector<int>& devs, bool round_trip = false, const std::vector<double>& tol = {},
+                  int levels = 1) {
     const size_t nc = r.comp_idxs.size();
     std::vector<Chunk> chunks = plan_chunks(r, nc, chunk_cells(run_cells(r, nc), devs.size()));
     auto jobs_of = [&](const Chunk& c, const Packed& p) {
@@ -331,7 +360,7 @@ void compress_run(const RunIndex& r, double keep, const std::filesystem::path& d
         for (size_t i = next.fetch_add(1); i < chunks.size(); i = next.fetch_add(1)) {
             Chunk& c = chunks[i];
             load_chunk(r, c, threads);
-            auto p = std::make_shared<Packed>(forward_chunk(c, keep, round_trip, tol));
+            auto p = std::make_shared<Packed>(forward_chunk(c, keep, round_trip, tol, levels));
             std::vector<XzJob> jobs = jobs_of(c, *p);
             if (xz_done.valid()) xz_done.get();
             xz_done = std::async(std::launch::async,
@@ -346,8 +375,17 @@ void compress_run(const RunIndex& r, double keep, const std::filesystem::path& d
 
 }  // namespace
 
+// `levels=`: logged as rmse= is.
+static int levels_of_run(const Config& cfg) {
+    if (cfg.levels > 1)
+        log_info("levels=" + std::to_string(cfg.levels) +
+                 " given: every box is transformed with up to that many levels, as its dimensions admit (not a "
+                 "reference parameter; the reference cannot decode these files)");
+    return cfg.levels;
+}
+
 int compress(const Config& cfg) {
-    if (cfg.rmse_error) return 1;
+    if (cfg.rmse_error || cfg.levels_error) return 1;
     if (cfg.xz_preset >= 0) set_xz_preset((uint32_t)cfg.xz_preset);
     if (xz_preset() != 6) log_info("xz preset " + std::to_string(xz_preset() & 0xff) +
                                    ((xz_preset() & 0x80000000u) ? "e" : "") + " (the reference's is 6)");
@@ -374,7 +412,8 @@ int compress(const Config& cfg) {
     log_info("Successfully processed data in " + fmt_double(since(t0)) + " seconds. Beginning compression...");
     const auto t1 = Clock::now();
     compress_run(r, (double)cfg.keep, std::filesystem::path(cfg.compressed_dir),
-                 [](size_t, const Chunk&, const Packed&) {}, run_devices(), false, slot_tolerances(cfg, r));
+                 [](size_t, const Chunk&, const Packed&) {}, run_devices(), false, slot_tolerances(cfg, r),
+                 levels_of_run(cfg));
     log_info("Compression completed in " + fmt_double(since(t1)) + " seconds.");
     return 0;
 }
@@ -449,7 +488,7 @@ int decompress(const Config& cfg) {
 }
 
 int estimate(Config& cfg) {
-    if (cfg.rmse_error) return 1;
+    if (cfg.rmse_error || cfg.levels_error) return 1;
     const int num_components = (int)cfg.components.size();
     TempDir scratch;
     const std::vector<std::string> files = format_files(cfg.data_dir, cfg.min_time, cfg.min_time);
@@ -488,7 +527,7 @@ int estimate(Config& cfg) {
             maxv[k] = std::max(maxv[k], hi[k]);
         }
         chunk_rmse[ci] = p.rmse;
-    }, run_devices(), /*round_trip=*/true, slot_tolerances(cfg, r));
+    }, run_devices(), /*round_trip=*/true, slot_tolerances(cfg, r), levels_of_run(cfg));
     for (const auto& [ci, rm] : chunk_rmse)
         for (size_t u = 0; u < rm.size(); ++u) all_rmses[u % nc].push_back(rm[u]);
     // The reference reads every file back (src/modes.cpp:250-265) and exits on

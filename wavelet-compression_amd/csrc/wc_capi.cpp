@@ -98,6 +98,44 @@ int forward_staged(wc_ctx* c, const void* d_cells, int dtype, int n, double keep
     return rc ? rc : stage_emit(c, n, keep, nullptr, d_payload, d_offsets, d_kept, d_rows);
 }
 
+// A call's small host arrays (tolerances, levels, work lists) reach the device
+// through the context's pinned block, so the caller's arrays are consumed before
+// the call returns.  pin_begin: the block, at least in_bytes long and no longer
+// read by the previous call's copy, and tol_in of dev_bytes; pin_upload: the
+// block's first in_bytes to tol_in on the stream.
+int pin_begin(wc_ctx* c, size_t in_bytes, size_t dev_bytes, uint8_t** pin) {
+    int rc;
+    hipError_t e;
+    if ((rc = ensure(c, c->tol_in, dev_bytes))) return rc;
+    if (!c->tol_ev && (e = hipEventCreateWithFlags(&c->tol_ev, hipEventDisableTiming)) != hipSuccess)
+        return hip_fail(c, e, "event");
+    // the previous call's copy out of the pinned block has finished
+    if (c->tol_ev_live && (e = hipEventSynchronize(c->tol_ev)) != hipSuccess) return hip_fail(c, e, "pinned upload");
+    c->tol_ev_live = false;
+    if (c->tol_pin_bytes < in_bytes) {
+        if (c->tol_pin) (void)hipHostFree(c->tol_pin);
+        c->tol_pin = nullptr;
+        c->tol_pin_bytes = 0;
+        const size_t want = std::max(in_bytes, size_t(4096));
+        if ((e = hipHostMalloc(&c->tol_pin, want, hipHostMallocDefault)) != hipSuccess) {
+            c->tol_pin = nullptr;
+            return fail(c, WC_ERR_NOMEM, std::string("pinned block: ") + hipGetErrorString(e));
+        }
+        c->tol_pin_bytes = want;
+    }
+    *pin = (uint8_t*)c->tol_pin;
+    return WC_OK;
+}
+
+int pin_upload(wc_ctx* c, size_t in_bytes) {
+    hipError_t e;
+    if ((e = hipMemcpyAsync(c->tol_in.p, c->tol_pin, in_bytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
+        (e = hipEventRecord(c->tol_ev, c->stream)) != hipSuccess)
+        return hip_fail(c, e, "pinned upload");
+    c->tol_ev_live = true;
+    return WC_OK;
+}
+
 // RMSE-tolerance mode, between the dense staging and the emit: unit u's
 // threshold (and model bound) from its own magnitude bins (wc_tol.hip).  The
 // tolerances and the solo / split layout of this call go through the context's
@@ -127,35 +165,16 @@ int stage_tol(wc_ctx* c, int n, const double* tol, float* d_thresh, double* d_bo
                  in_bytes = o_split + 4 * nsplit, o_thresh = round_up(in_bytes, 8);
     int rc;
     hipError_t e;
-    if ((rc = ensure(c, c->tol_in, o_thresh + sizeof(float) * n)) ||
-        (nsplit && (rc = ensure(c, c->tol_bins, sizeof(uint32_t) * WC_HIST_BINS * nsplit))))
+    uint8_t* pin = nullptr;
+    if ((nsplit && (rc = ensure(c, c->tol_bins, sizeof(uint32_t) * WC_HIST_BINS * nsplit))) ||
+        (rc = pin_begin(c, in_bytes, o_thresh + sizeof(float) * n, &pin)))
         return rc;
-    if (!c->tol_ev && (e = hipEventCreateWithFlags(&c->tol_ev, hipEventDisableTiming)) != hipSuccess)
-        return hip_fail(c, e, "event");
-    // the previous call's copy out of the pinned block has finished
-    if (c->tol_ev_live && (e = hipEventSynchronize(c->tol_ev)) != hipSuccess) return hip_fail(c, e, "tolerance upload");
-    c->tol_ev_live = false;
-    if (c->tol_pin_bytes < in_bytes) {
-        if (c->tol_pin) (void)hipHostFree(c->tol_pin);
-        c->tol_pin = nullptr;
-        c->tol_pin_bytes = 0;
-        const size_t want = std::max(in_bytes, size_t(4096));
-        if ((e = hipHostMalloc(&c->tol_pin, want, hipHostMallocDefault)) != hipSuccess) {
-            c->tol_pin = nullptr;
-            return fail(c, WC_ERR_NOMEM, std::string("pinned tolerances: ") + hipGetErrorString(e));
-        }
-        c->tol_pin_bytes = want;
-    }
-    uint8_t* pin = (uint8_t*)c->tol_pin;
     std::memcpy(pin, tol, sizeof(double) * n);
     if (nitems) std::memcpy(pin + o_items, items.data(), sizeof(uint2) * nitems);
     std::memcpy(pin + o_slot, slot.data(), 4ull * n);
     if (nsplit) std::memcpy(pin + o_split, split.data(), 4 * nsplit);
+    if ((rc = pin_upload(c, in_bytes))) return rc;
     uint8_t* d = (uint8_t*)c->tol_in.p;
-    if ((e = hipMemcpyAsync(d, pin, in_bytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
-        (e = hipEventRecord(c->tol_ev, c->stream)) != hipSuccess)
-        return hip_fail(c, e, "tolerance upload");
-    c->tol_ev_live = true;
     if (nsplit && (e = hipMemsetAsync(c->tol_bins.p, 0, sizeof(uint32_t) * WC_HIST_BINS * nsplit, c->stream)) !=
                       hipSuccess)
         return hip_fail(c, e, "memset bins");
@@ -167,6 +186,87 @@ int stage_tol(wc_ctx* c, int n, const double* tol, float* d_thresh, double* d_bo
     if (e != hipSuccess) return hip_fail(c, e, "tolerance launch");
     *uthresh = th;
     return WC_OK;
+}
+
+// Multi-level mode (wc_levels.hip).  The levels and the work lists of one call,
+// on the device (in tol_in, uploaded through the pinned block): the levels are
+// not part of the cached plan, which is keyed by the units alone.
+struct LevelWork {
+    const int32_t* levels = nullptr;  // [n]
+    const uint2* hdr = nullptr;       // (unit, L) of the units with L >= 2
+    const uint2* key = nullptr;       // (unit, first flat tile) runs of kLevelKeyChunk tiles of those units
+    const uint2* lv[WC_MAX_LEVELS - 1] = {};  // level l's (unit, chunk) items at lv[l - 2]
+    uint32_t nhdr = 0, nkey = 0, nlv[WC_MAX_LEVELS - 1] = {};
+    int maxl = 1;
+};
+constexpr uint32_t kLevelKeyChunk = 8;  // flat tiles per workgroup of the key pass
+
+int upload_levels(wc_ctx* c, int n, const int32_t* levels, LevelWork* w) {
+    const Plan& P = c->plan;
+    std::vector<uint2> hdr, key, lv[WC_MAX_LEVELS - 1];
+    const uint32_t cb = level_chunk_blocks();
+    for (int u = 0; u < n; ++u) {
+        const int L = levels[u];
+        if (L < 2) continue;
+        w->maxl = std::max(w->maxl, L);
+        hdr.push_back(make_uint2((uint32_t)u, (uint32_t)L));
+        const UnitDev& d = P.units[u];
+        for (uint32_t t = 0; t < d.nftiles; t += kLevelKeyChunk) key.push_back(make_uint2((uint32_t)u, t));
+        for (int l = 2; l <= L; ++l) {
+            const uint64_t nblk = d.ncells >> (3 * l);  // 2x2x2 blocks of the level's sub-box
+            for (uint64_t b = 0; b < nblk; b += cb) lv[l - 2].push_back(make_uint2((uint32_t)u, (uint32_t)(b / cb)));
+        }
+    }
+    size_t items = hdr.size() + key.size();
+    for (const auto& v : lv) items += v.size();
+    const size_t o_levels = sizeof(uint2) * items, in_bytes = o_levels + sizeof(int32_t) * n;
+    int rc;
+    uint8_t* pin = nullptr;
+    if ((rc = pin_begin(c, in_bytes, in_bytes, &pin))) return rc;
+    const uint8_t* d = (const uint8_t*)c->tol_in.p;
+    size_t o = 0;
+    auto put = [&](const std::vector<uint2>& v, const uint2** dev, uint32_t* count) {
+        if (!v.empty()) std::memcpy(pin + o, v.data(), sizeof(uint2) * v.size());
+        *dev = (const uint2*)(d + o);
+        *count = (uint32_t)v.size();
+        o += sizeof(uint2) * v.size();
+    };
+    put(hdr, &w->hdr, &w->nhdr);
+    put(key, &w->key, &w->nkey);
+    for (int i = 0; i < WC_MAX_LEVELS - 1; ++i) put(lv[i], &w->lv[i], &w->nlv[i]);
+    std::memcpy(pin + o_levels, levels, sizeof(int32_t) * n);
+    w->levels = (const int32_t*)(d + o_levels);
+    if ((rc = ensure(c, c->lv_side, sizeof(float) * (P.coef_extent / 8 + 64)))) return rc;
+    return pin_upload(c, in_bytes);
+}
+
+// The level passes on the coefficient scratch: analysis l = 2..L after the
+// one-level transform (with_key: then the units' max keys of the final array,
+// for the keep rule), or synthesis l = L..2 before the one-level inverse.
+// bad (inverse of payloads): per-unit words the decode set for a header that disagrees.
+int run_levels(wc_ctx* c, const LevelWork& w, bool fwd, bool with_key, const uint32_t* bad = nullptr) {
+    const UnitDev* du = (const UnitDev*)c->plan.d_units.p;
+    float* coef = (float*)c->coef.p;
+    float* side = (float*)c->lv_side.p;
+    unsigned long long* key = (unsigned long long*)((uint8_t*)c->state.p + 16);
+    StageTimer t(c, WC_STAGE_LEVELS);
+    hipError_t e = hipSuccess;
+    if (fwd) {
+        for (int l = 2; l <= w.maxl && e == hipSuccess; ++l)
+            e = launch_level(c->stream, true, du, w.lv[l - 2], w.nlv[l - 2], l - 1, coef, side,
+                             with_key && l == 2 ? key : nullptr, nullptr);
+        if (e == hipSuccess && with_key) e = launch_level_key(c->stream, du, w.key, w.nkey, kLevelKeyChunk, coef, key);
+    } else {
+        for (int l = w.maxl; l >= 2 && e == hipSuccess; --l)
+            e = launch_level(c->stream, false, du, w.lv[l - 2], w.nlv[l - 2], l - 1, coef, side, nullptr, bad);
+    }
+    return e == hipSuccess ? WC_OK : hip_fail(c, e, "level pass launch");
+}
+
+bool single_level(const int32_t* levels, int n) {
+    for (int i = 0; i < n; ++i)
+        if (levels[i] != 1) return false;
+    return true;
 }
 
 }  // namespace
@@ -218,7 +318,8 @@ void wc_ctx_destroy(wc_ctx* c) {
                       &c->plan.d_units,  &c->plan.d_xtiles,  &c->plan.d_ftiles,  &c->plan.d_dtiles,
                       &c->plan.d_edesc, &c->plan.d_ixtiles, &c->plan.d_rtiles,
                       &c->plan.d_rdtiles, &c->rowinfo,    &c->istate,        &c->npairs,
-                      &c->tol_in,        &c->tol_bins,       &c->h_thresh,       &c->h_bound};
+                      &c->tol_in,        &c->tol_bins,       &c->h_thresh,       &c->h_bound,
+                      &c->lv_side};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (Plan& P : c->plan_cache) free_plan(P);
@@ -745,6 +846,135 @@ int wc_inverse_flat(wc_ctx* c, const float* d_flat, const wc_unit* units, int n,
     StageTimer t(c, WC_STAGE_INVERSE);
     hipError_t e = launch_inverse(c->stream, d_flat, 1, (const UnitDev*)P.d_units.p, (const XTile*)P.d_xtiles.p,
                                   P.ngen, P.lds_inverse, P.nfast, P.lds_fast, d_out);
+    return e == hipSuccess ? WC_OK : hip_fail(c, e, "inverse launch");
+}
+
+// Multi-level forward: the one-level transform staged densely, the level
+// passes, then the emit on the final array and ncoeff = -L into the headers of
+// the units with L >= 2.  Leaves nothing staged.
+int wc_forward_levels(wc_ctx* c, const void* d_cells, int dtype, const wc_unit* units, int n, const int32_t* levels,
+                      double keep, const float* thresh, uint8_t* d_payload, uint64_t cap, uint64_t* d_offsets,
+                      uint32_t* d_kept) {
+    if (!c) return WC_ERR_INVALID;
+    int rc;
+    if ((rc = validate_units(c, units, n))) return rc;
+    if (dtype != WC_F32 && dtype != WC_F64) return fail(c, WC_ERR_INVALID, "dtype");
+    if (n == 0) return WC_OK;
+    if (!d_cells || !d_payload || !d_offsets || !d_kept) return fail(c, WC_ERR_INVALID, "null buffer");
+    if ((rc = validate_levels(c, units, n, levels))) return rc;
+    if (cap < wc_payload_bound(units, n)) return fail(c, WC_ERR_INVALID, "payload_capacity < wc_payload_bound");
+    if ((rc = check_aligned(c, d_cells, "cells")) || (rc = check_aligned(c, d_payload, "payload")) ||
+        (rc = check_aligned(c, d_offsets, "offsets", 8)) || (rc = check_aligned(c, d_kept, "kept", 4)))
+        return rc;
+    if ((rc = set_device(c)) || (rc = get_plan(c, units, n))) return rc;
+    if ((rc = ensure_scratch(c))) return rc;
+    if (single_level(levels, n) && !thresh)  // wc_forward itself
+        return forward_staged(c, d_cells, dtype, n, keep, d_payload, d_offsets, d_kept);
+    LevelWork w;
+    // dense staging: the level passes and the final threshold need every coefficient
+    if ((rc = upload_levels(c, n, levels, &w)) || (rc = stage_transform(c, d_cells, dtype, 0.0, false)) ||
+        (rc = run_levels(c, w, true, !thresh)) || (rc = stage_emit(c, n, keep, thresh, d_payload, d_offsets, d_kept)))
+        return rc;
+    StageTimer t(c, WC_STAGE_LEVELS);
+    hipError_t e = launch_level_headers(c->stream, (const UnitDev*)c->plan.d_units.p, w.hdr, w.nhdr, d_payload);
+    return e == hipSuccess ? WC_OK : hip_fail(c, e, "level header launch");
+}
+
+int wc_decompose_levels(wc_ctx* c, const void* d_cells, int dtype, const wc_unit* units, int n, const int32_t* levels,
+                        float* d_flat) {
+    if (!c) return WC_ERR_INVALID;
+    int rc;
+    if ((rc = validate_units(c, units, n))) return rc;
+    if (dtype != WC_F32 && dtype != WC_F64) return fail(c, WC_ERR_INVALID, "dtype");
+    if (n == 0) return WC_OK;
+    if (!d_cells || !d_flat) return fail(c, WC_ERR_INVALID, "null buffer");
+    if ((rc = validate_levels(c, units, n, levels))) return rc;
+    if (single_level(levels, n)) return wc_decompose(c, d_cells, dtype, units, n, d_flat);
+    if ((rc = check_aligned(c, d_cells, "cells")) || (rc = check_aligned(c, d_flat, "flat"))) return rc;
+    if ((rc = set_device(c)) || (rc = get_plan(c, units, n)) || (rc = ensure_scratch(c))) return rc;
+    // through the coefficient scratch (aligned units, the side scratch beside it), then out
+    LevelWork w;
+    if ((rc = upload_levels(c, n, levels, &w)) || (rc = stage_transform(c, d_cells, dtype, 0.0, false)) ||
+        (rc = run_levels(c, w, true, false)))
+        return rc;
+    const Plan& P = c->plan;
+    StageTimer t(c, WC_STAGE_LEVELS);
+    hipError_t e = launch_level_flat(c->stream, (const UnitDev*)P.d_units.p, (const FTile*)P.d_ftiles.p,
+                                     (uint32_t)P.ftiles.size(), (float*)c->coef.p, d_flat, 1);
+    return e == hipSuccess ? WC_OK : hip_fail(c, e, "flat copy launch");
+}
+
+int wc_inverse_flat_levels(wc_ctx* c, const float* d_flat, const wc_unit* units, int n, const int32_t* levels,
+                           float* d_out) {
+    if (!c) return WC_ERR_INVALID;
+    int rc;
+    if ((rc = validate_units(c, units, n))) return rc;
+    if (n == 0) return WC_OK;
+    if (!d_flat || !d_out) return fail(c, WC_ERR_INVALID, "null buffer");
+    if ((rc = validate_levels(c, units, n, levels))) return rc;
+    if (single_level(levels, n)) return wc_inverse_flat(c, d_flat, units, n, d_out);
+    if ((rc = check_aligned(c, d_flat, "flat")) || (rc = check_aligned(c, d_out, "out"))) return rc;
+    if ((rc = set_device(c)) || (rc = get_plan(c, units, n)) || (rc = ensure_scratch(c))) return rc;
+    LevelWork w;
+    if ((rc = upload_levels(c, n, levels, &w))) return rc;
+    const Plan& P = c->plan;
+    hipError_t e;
+    {
+        StageTimer t(c, WC_STAGE_LEVELS);
+        e = launch_level_flat(c->stream, (const UnitDev*)P.d_units.p, (const FTile*)P.d_ftiles.p,
+                              (uint32_t)P.ftiles.size(), (float*)c->coef.p, const_cast<float*>(d_flat), 0);
+        if (e != hipSuccess) return hip_fail(c, e, "flat copy launch");
+    }
+    if ((rc = run_levels(c, w, false, false))) return rc;
+    StageTimer t(c, WC_STAGE_INVERSE);
+    e = launch_inverse(c->stream, (const float*)c->coef.p, 0, (const UnitDev*)P.d_units.p, (const XTile*)P.d_xtiles.p,
+                       P.ngen, P.lds_inverse, P.nfast, P.lds_fast, d_out);
+    return e == hipSuccess ? WC_OK : hip_fail(c, e, "inverse launch");
+}
+
+// Multi-level inverse: every unit through the dense decode (the plan of
+// WC_OPT_INVERSE_ROWS = 0), the synthesis passes on the coefficient scratch,
+// then the one-level inverse of all units.
+int wc_inverse_levels(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                      const int32_t* levels, float* d_out) {
+    if (!c) return WC_ERR_INVALID;
+    int rc;
+    if ((rc = validate_units(c, units, n))) return rc;
+    if (n == 0) return WC_OK;
+    if (!d_payload || !d_offsets || !d_out) return fail(c, WC_ERR_INVALID, "null buffer");
+    if ((rc = validate_levels(c, units, n, levels))) return rc;
+    if (single_level(levels, n)) return wc_inverse(c, d_payload, d_offsets, units, n, d_out);
+    if ((rc = check_aligned(c, d_payload, "payload")) || (rc = check_aligned(c, d_offsets, "offsets", 8)) ||
+        (rc = check_aligned(c, d_out, "out")))
+        return rc;
+    if ((rc = set_device(c))) return rc;
+    const bool rows = c->opt_inv_rows;
+    c->opt_inv_rows = false;  // the plan's key holds it: this batch's dense plan is cached beside the default one
+    rc = get_plan(c, units, n);
+    c->opt_inv_rows = rows;
+    if (rc || (rc = ensure_scratch(c))) return rc;
+    LevelWork w;
+    if ((rc = upload_levels(c, n, levels, &w))) return rc;
+    const Plan& P = c->plan;
+    uint8_t* st = (uint8_t*)c->state.p;
+    hipError_t e = hipMemsetAsync(st, 0, decode_state_bytes(P), c->stream);  // tickets and look-back status
+    if (e != hipSuccess) return hip_fail(c, e, "memset");
+    // per-unit "header disagrees" words, written by each unit's first decode tile (a unit
+    // without cells has neither decode nor inverse tiles); npairs is free: no unit is row-indexed
+    uint32_t* bad = (uint32_t*)c->npairs.p;
+    {
+        StageTimer t(c, WC_STAGE_DECODE);
+        e = launch_decode(c->stream, (const UnitDev*)P.d_units.p, (const FTile*)P.d_dtiles.p, (uint32_t)P.dtiles.size(),
+                          nullptr, 0u, nullptr, 0u, d_payload, d_offsets, (uint32_t*)st,
+                          (unsigned long long*)(st + round_up(4ull * n, 8)), (float*)c->coef.p, nullptr,
+                          (uint32_t*)c->errflag.p, use_ordered(c) ? (c->opt_reverse ? 2 : 1) : 0, bad, w.levels);
+        if (e != hipSuccess) return hip_fail(c, e, "decode launch");
+    }
+    c->err_check_pending = true;  // malformed payloads surface at the next wc_synchronize
+    if ((rc = run_levels(c, w, false, false, bad))) return rc;
+    StageTimer t(c, WC_STAGE_INVERSE);
+    e = launch_inverse(c->stream, (const float*)c->coef.p, 0, (const UnitDev*)P.d_units.p, (const XTile*)P.d_ixtiles.p,
+                       P.ign, P.lds_inverse, P.ifast, P.lds_fast, d_out, bad);
     return e == hipSuccess ? WC_OK : hip_fail(c, e, "inverse launch");
 }
 

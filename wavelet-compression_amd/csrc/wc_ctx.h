@@ -16,6 +16,9 @@
 //   wc_tolhost.cpp   host side of the RMSE-tolerance mode: the selection rule
 //                    on one unit's counts, the mode's argument checks and
 //                    wc_forward_tol_host (unit runs one after another)
+//   wc_levelshost.cpp host side of the multi-level mode: wc_levels_for,
+//                    wc_payload_levels, the mode's argument checks and the
+//                    _levels_host entry points
 #pragma once
 
 #include "wavelet_amd.h"
@@ -48,13 +51,14 @@ hipError_t launch_transform_fallback(hipStream_t, const void*, int, const UnitDe
 hipError_t launch_pack(hipStream_t, const UnitDev*, int, const uint32_t*, const uint8_t*, uint64_t*, uint8_t*);
 hipError_t launch_decode(hipStream_t, const UnitDev*, const FTile*, uint32_t, const FTile*, uint32_t,
                          unsigned long long*, uint32_t, const uint8_t*, const uint64_t*, uint32_t*,
-                         unsigned long long*, float*, uint2*, uint32_t*, int, uint32_t*);
+                         unsigned long long*, float*, uint2*, uint32_t*, int, uint32_t*,
+                         const int32_t* levels = nullptr);
 hipError_t launch_pair_counts(hipStream_t, const UnitDev*, int, const uint8_t*, const uint64_t*, uint32_t*, uint32_t*);
 hipError_t launch_inverse_rows(hipStream_t, const RTile*, uint32_t, size_t, uint32_t, const uint8_t*,
                                const uint64_t*, const uint2*, float*, int, const void*, int, const UnitDev*, int,
                                double*, double*, bool, const uint32_t*);
 hipError_t launch_inverse(hipStream_t, const float*, int, const UnitDev*, const XTile*, uint32_t, size_t, uint32_t,
-                          size_t, float*);
+                          size_t, float*, const uint32_t* bad = nullptr);
 hipError_t launch_rmse(hipStream_t, const void*, int, const float*, const UnitDev*, int, const FTile*,
                        uint32_t, double*, double*);
 hipError_t launch_emit(hipStream_t, const EmitParams&, const float*, uint32_t, uint32_t);
@@ -62,6 +66,17 @@ hipError_t launch_hist(hipStream_t, const UnitDev*, const FTile*, uint32_t, cons
                        unsigned long long*, bool);
 hipError_t launch_tol(hipStream_t, const UnitDev*, int, const uint32_t*, const uint2*, uint32_t, uint32_t,
                       const uint32_t*, uint32_t, const float*, uint32_t*, const double*, float*, double*);
+// wc_levels.hip: one level pass (analysis or synthesis into the side scratch, then
+// the copy back), the key pass over the final array, the header patch, and the
+// copy between the coefficient scratch and a caller's flat buffer
+hipError_t launch_level(hipStream_t, bool fwd, const UnitDev*, const uint2* items, uint32_t nitems, int shift,
+                        float* coef, float* side, unsigned long long* key, const uint32_t* bad);
+hipError_t launch_level_key(hipStream_t, const UnitDev*, const uint2* items, uint32_t nitems, uint32_t chunk,
+                            const float* coef, unsigned long long* key);
+hipError_t launch_level_headers(hipStream_t, const UnitDev*, const uint2* items, uint32_t nitems, uint8_t* payload);
+hipError_t launch_level_flat(hipStream_t, const UnitDev*, const FTile*, uint32_t ntiles, float* coef, float* flat,
+                             int to_flat);
+uint32_t level_chunk_blocks();
 
 struct DevBuf {
     void* p = nullptr;
@@ -176,6 +191,10 @@ struct wc_ctx {
     wc::DevBuf tol_in;            // tol[n] | slot[n] | split_units[nsplit] | items[nitems] | thresh[n]
     wc::DevBuf tol_bins;          // kHistBins uint32 per split unit (none without split units)
     wc::DevBuf h_thresh, h_bound; // wc_forward_tol_host: per-unit thresholds and bounds
+    // multi-level mode (wc_forward_levels / wc_inverse_levels): the side scratch
+    // of the level passes (coef_extent / 8 floats); the call's levels and work
+    // lists go through the same pinned block and tol_in
+    wc::DevBuf lv_side;
     std::unique_ptr<wc::HostPool> hpool;
     // uploads from pageable host memory: copied by upool's threads into pinned
     // bounce slots, each slot's copy to the device ordered by an event
@@ -226,6 +245,9 @@ int host_threads_default();
 
 // wc_tolhost.cpp
 int validate_tol(wc_ctx* c, const wc_unit* units, int n, const double* tol);
+
+// wc_levelshost.cpp
+int validate_levels(wc_ctx* c, const wc_unit* units, int n, const int32_t* levels);
 
 // Bracket one launch with events when profiling is on.
 struct StageTimer {

@@ -43,11 +43,17 @@ constexpr int kDecChunk = 4096;                   // floats per write round (16 
 
 // Header check: the dims and ncoeff must be the unit's and nrle >= 0.  More
 // pairs than coefficients are accepted: rle_decode drops every pair whose
-// index reaches ncoeff (src/decompressor.cpp:20-27), as here.
-__device__ __forceinline__ bool read_header(const UnitDev& U, const uint8_t* __restrict__ ph, int32_t& nrle) {
+// index reaches ncoeff (src/decompressor.cpp:20-27), as here.  `want`: the
+// ncoeff field the caller expects, W*H*D, or -L for a multi-level unit
+// (wc_inverse_levels): every other path rejects such a payload here.
+__device__ __forceinline__ bool read_header(const UnitDev& U, const uint8_t* __restrict__ ph, int32_t& nrle,
+                                            int32_t want) {
     const int32_t* h = reinterpret_cast<const int32_t*>(ph);
     nrle = h[4];
-    return h[0] == U.nx && h[1] == U.ny && h[2] == U.nz && h[3] == (int32_t)U.ncells && nrle >= 0;
+    return h[0] == U.nx && h[1] == U.ny && h[2] == U.nz && h[3] == want && nrle >= 0;
+}
+__device__ __forceinline__ bool read_header(const UnitDev& U, const uint8_t* __restrict__ ph, int32_t& nrle) {
+    return read_header(U, ph, nrle, (int32_t)U.ncells);
 }
 
 // The same with saturating adds (v_add_u32 clamp): positions at or past
@@ -199,12 +205,18 @@ __global__ __launch_bounds__(kThreads, WC_RIX_MINB) void k_rowindex(const UnitDe
     }
 }
 
+// LV (wc_inverse_levels): unit u's header must carry levels[u] (ncoeff = -L for
+// L >= 2).  A unit whose header disagrees is left alone: nothing past the
+// header is read, nothing is decoded, kErrHeader is raised and bad[u] tells the
+// level passes and the one-level inverse (later launches) to skip the unit.
+template <bool LV>
 __global__ __launch_bounds__(kThreads) void k_decode(const UnitDev* __restrict__ units,
                                                    const FTile* __restrict__ tiles,
                                                    const uint8_t* __restrict__ payload,
                                                    const uint64_t* __restrict__ offsets, uint32_t* __restrict__ ticket,
                                                    unsigned long long* __restrict__ status, float* __restrict__ flat,
-                                                   uint32_t* __restrict__ err, int ordered) {
+                                                   uint32_t* __restrict__ err, int ordered,
+                                                   const int32_t* __restrict__ levels, uint32_t* __restrict__ bad) {
     __shared__ __attribute__((aligned(16))) float buf[kDecChunk];
     __shared__ unsigned long long s_w[4];
     __shared__ unsigned long long s_x[2];
@@ -214,7 +226,17 @@ __global__ __launch_bounds__(kThreads) void k_decode(const UnitDev* __restrict__
     const UnitDev& U = units[u];
     const uint8_t* ph = payload + offsets[u];
     int32_t nrle;
-    const bool hok = read_header(U, ph, nrle);
+    bool hok;
+    if constexpr (LV) {
+        hok = read_header(U, ph, nrle, levels[u] >= 2 ? -levels[u] : (int32_t)U.ncells);
+        if (ft.index == 0 && tid == 0) {
+            bad[u] = hok ? 0u : 1u;
+            if (!hok) atomicOr(err, kErrHeader);
+        }
+        if (!hok) return;  // uniform
+    } else {
+        hok = read_header(U, ph, nrle);
+    }
     const int64_t n = hok ? nrle : 0;
     const uint32_t ntile = n ? (uint32_t)((n + kFlatTile - 1) / kFlatTile) : 1u;
     // The plan launches ceil(ncoeff / kFlatTile) blocks per unit; those whose
@@ -327,13 +349,16 @@ __global__ __launch_bounds__(kThreads) void k_decode(const UnitDev* __restrict__
 // Phase 1: flat rows (contiguous along K) -> LDS.  Phase 2: per block X, then Y,
 // then Z synthesis (src/decompressor.cpp:89-156); blocks with an odd tail on any
 // axis reconstruct to 0 (the reference's zero-initialised `restored`).
+template <bool SKIP>
 __global__ __launch_bounds__(kThreads) void k_inverse(const float* __restrict__ flat,
                                                     int flat_at_cell_off,
                                                     const UnitDev* __restrict__ units,
                                                     const XTile* __restrict__ tiles,
-                                                    float* __restrict__ out) {
+                                                    float* __restrict__ out, const uint32_t* __restrict__ bad) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const XTile td = tiles[blockIdx.x];
+    if constexpr (SKIP)  // wc_inverse_levels: a unit whose header disagreed stays untouched
+        if (bad[td.unit]) return;
     const UnitDev& U = units[td.unit];
     const int W = U.nx, H = U.ny, D = U.nz;
     const int hx = U.hx, hy = U.hy, hz = U.hz;
@@ -440,13 +465,16 @@ __global__ __launch_bounds__(kThreads) void k_inverse(const float* __restrict__ 
 // thread owns a column of 4 consecutive z-blocks.  Flat rows are staged with
 // 16-B loads; each of the 8 sub-band values is read back as one float4 (the 4
 // z-blocks), then X, Y, Z synthesis per block and 8-B x-pair stores.
+template <bool SKIP>
 __global__ __launch_bounds__(kThreads) void k_inverse_fast(const float* __restrict__ flat,
                                                          int flat_at_cell_off,
                                                          const UnitDev* __restrict__ units,
                                                          const XTile* __restrict__ tiles,
-                                                         float* __restrict__ out) {
+                                                         float* __restrict__ out, const uint32_t* __restrict__ bad) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const XTile td = tiles[blockIdx.x];
+    if constexpr (SKIP)
+        if (bad[td.unit]) return;
     const UnitDev& U = units[td.unit];
     const int W = U.nx, H = U.ny, D = U.nz;
     const int hx = U.hx, hy = U.hy, hz = U.hz;
@@ -1129,11 +1157,18 @@ hipError_t launch_decode(hipStream_t st, const UnitDev* units, const FTile* ftil
                          const FTile* rtiles, uint32_t nrt, unsigned long long* istate, uint32_t epoch,
                          const uint8_t* payload, const uint64_t* offsets, uint32_t* ticket,
                          unsigned long long* status, float* flat, uint2* rowinfo, uint32_t* err, int ordered,
-                         uint32_t* npairs) {
+                         uint32_t* npairs, const int32_t* levels) {
+    // wc_inverse_levels: every unit decodes densely, and npairs (unused without
+    // row-indexed units) takes the per-unit "header disagrees" words
     if (nrt)
         k_rowindex<<<nrt, kThreads, 0, st>>>(units, rtiles, ticket, payload, offsets, istate, rowinfo, err, ordered,
                                              epoch, npairs);
-    if (nft) k_decode<<<nft, kThreads, 0, st>>>(units, ftiles, payload, offsets, ticket, status, flat, err, ordered);
+    if (nft && !levels)
+        k_decode<false><<<nft, kThreads, 0, st>>>(units, ftiles, payload, offsets, ticket, status, flat, err, ordered,
+                                                  nullptr, nullptr);
+    if (nft && levels)
+        k_decode<true><<<nft, kThreads, 0, st>>>(units, ftiles, payload, offsets, ticket, status, flat, err, ordered,
+                                                 levels, npairs);
     return hipGetLastError();
 }
 
@@ -1141,9 +1176,16 @@ hipError_t launch_decode(hipStream_t st, const UnitDev* units, const FTile* ftil
 // k_inverse_fast (the plan's xtiles order).
 hipError_t launch_inverse(hipStream_t st, const float* flat, int flat_at_cell_off, const UnitDev* units,
                           const XTile* tiles, uint32_t ngen, size_t lds_gen, uint32_t nfast, size_t lds_fast,
-                          float* out) {
-    if (ngen) k_inverse<<<ngen, kThreads, lds_gen, st>>>(flat, flat_at_cell_off, units, tiles, out);
-    if (nfast) k_inverse_fast<<<nfast, kThreads, lds_fast, st>>>(flat, flat_at_cell_off, units, tiles + ngen, out);
+                          float* out, const uint32_t* bad) {
+    if (bad) {  // wc_inverse_levels: units flagged by the decode are skipped
+        if (ngen) k_inverse<true><<<ngen, kThreads, lds_gen, st>>>(flat, flat_at_cell_off, units, tiles, out, bad);
+        if (nfast)
+            k_inverse_fast<true><<<nfast, kThreads, lds_fast, st>>>(flat, flat_at_cell_off, units, tiles + ngen, out, bad);
+        return hipGetLastError();
+    }
+    if (ngen) k_inverse<false><<<ngen, kThreads, lds_gen, st>>>(flat, flat_at_cell_off, units, tiles, out, nullptr);
+    if (nfast)
+        k_inverse_fast<false><<<nfast, kThreads, lds_fast, st>>>(flat, flat_at_cell_off, units, tiles + ngen, out, nullptr);
     return hipGetLastError();
 }
 
