@@ -385,6 +385,67 @@ int wc_forward_levels_host(wc_ctx* ctx, const void* cells, int dtype, const wc_u
 int wc_inverse_levels_host(wc_ctx* ctx, const uint8_t* payload, const uint64_t* offsets, const wc_unit* units, int n,
                            const int32_t* levels, float* out);
 
+/* Opt-in reduced-resolution decode (not in the reference): the box at 1/2^r
+ * resolution straight from a payload, without the work of the full resolution.
+ * The low-pass corner of the coefficient array after undoing levels L..r+1 is
+ * that box; because the low-pass is (a + b) * 0.5f per axis, each of its cells
+ * is the mean of a 2^r x 2^r x 2^r block of the full reconstruction up to fp32
+ * rounding (the "average down" of AMR codes).  It works on one-level payloads
+ * too, the reference's own file format: r = 1 of an even-sized box.
+ *
+ * Definition.  A unit is W x H x D with L levels; its payload is as
+ * wc_forward_levels writes it (ncoeff = W*H*D for L = 1, -L for L >= 2).  The
+ * unit has a reduction r, 0 <= r <= L; for r >= 1 on a unit with cells 2^r must
+ * divide W, H and D (for L >= 2 the levels rule guarantees it; for L = 1, r = 1
+ * it means even dimensions).  Write (w, h, d) = (W, H, D) >> r.
+ *   1. A is the dense flat array of the payload in x-slowest order
+ *      (I*H + J)*D + K: rle_decode, pairs at or past W*H*D dropped.
+ *   2. Take the corner C(I, J, K) = A[(I*H + J)*D + K], I < w, J < h, K < d,
+ *      stored compactly as C[(I*h + J)*d + K].
+ *   3. r = L: the result is C read as a Box3D, out[x + w*(y + h*z)] = C(x, y, z);
+ *      no arithmetic runs.  r < L: the result is the multi-level inverse
+ *      (wc_inverse_flat_levels) of the flat array C of a w x h x d unit with
+ *      L - r levels; with L - r = 1 that is the plain inverse_wavelet_decompose.
+ *   4. r = 0 is wc_inverse_levels bit for bit.
+ * Step 3 is exact, not an approximation: the synthesis of level l touches only
+ * the corner (W, H, D) >> (l-1), so levels L..r+1 of the full inverse act on C
+ * exactly as levels L-r..1 act on a w x h x d unit.
+ * Property (finite data): every output cell differs from the mean of its
+ * 2^r-cube of the full reconstruction by at most 3*r * 2^-23 * max|full
+ * reconstruction| (one rounding of at most 2^-24 of a block mean per synthesis
+ * step, 3 axis steps per level, r levels, a factor 2 of margin).
+ *
+ *   wc_coarse_units: host-only; out[u] = units[u] with dims >> reduce[u], cell
+ *     offsets packed back to back, each start rounded up to 4 elements; *extent
+ *     = elements the output needs.  WC_ERR_INVALID for null pointers, negative
+ *     dims or a reduce outside 0..WC_MAX_LEVELS.
+ *   wc_inverse_coarse: units describe the payloads at full size (their
+ *     cell_offset is ignored); levels (HOST, NULL = all 1) and reduce (HOST)
+ *     are consumed before the call returns.  out_units[u] must carry exactly the
+ *     dims >> reduce[u]; its cell_offset is the caller's choice (any element
+ *     alignment; d_out itself 16-byte aligned).  A unit without cells keeps its
+ *     shifted dims and writes nothing.  For a unit with r >= 1 nothing of size
+ *     W*H*D is written or read: the pairs go straight to the compact corner in
+ *     context scratch, and pair tiles past the corner's end leave at once.  A
+ *     batch whose reduces are all 0 is wc_inverse_levels (wc_inverse when the
+ *     levels are all 1 too) on out_units.  Asynchronous; malformed payloads as
+ *     in wc_inverse_levels: a header that disagrees with (W, H, D, L) raises
+ *     WC_ERR_FORMAT at the next wc_synchronize, nothing past it is read and the
+ *     unit's output cells stay untouched while the other units decode; a
+ *     negative run raises the same error and writes nothing outside the unit's
+ *     own corner scratch and output range.
+ *   wc_inverse_coarse_host: host buffers; levels = NULL reads each L from its
+ *     header, as wc_inverse_levels_host does; the unit runs go one after another.
+ * A reduce outside 0..levels[u], a dimension that 2^r does not divide on a unit
+ * with cells, an out_units entry with other dims or reserved != 0, or a null
+ * buffer: WC_ERR_INVALID naming the unit, before anything is launched; outputs
+ * stay untouched. */
+int wc_coarse_units(const wc_unit* units, const int32_t* reduce, int n, wc_unit* out, uint64_t* extent);
+int wc_inverse_coarse(wc_ctx* ctx, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                      const int32_t* levels, const int32_t* reduce, const wc_unit* out_units, float* d_out);
+int wc_inverse_coarse_host(wc_ctx* ctx, const uint8_t* payload, const uint64_t* offsets, const wc_unit* units, int n,
+                           const int32_t* levels, const int32_t* reduce, const wc_unit* out_units, float* out);
+
 /* Transform only: cells -> flat fp32 coefficients (x-slowest order), written
  * at the same element offsets as the cells (d_flat has the cell buffer's extent). */
 int wc_decompose(wc_ctx* ctx, const void* d_cells, int dtype, const wc_unit* units, int n,

@@ -33,6 +33,7 @@ EXPORTED = (
     "wc_tol_threshold", "wc_forward_tol", "wc_forward_emit_tol", "wc_forward_tol_host",
     "wc_levels_for", "wc_payload_levels", "wc_forward_levels", "wc_decompose_levels",
     "wc_inverse_flat_levels", "wc_inverse_levels", "wc_forward_levels_host", "wc_inverse_levels_host",
+    "wc_coarse_units", "wc_inverse_coarse", "wc_inverse_coarse_host",
 )
 WC_MAX_LEVELS = 4  # levels of the opt-in multi-level transform (1 = the reference's codec)
 WC_OPT_SPARSE = 12   # sparse coefficient staging in the forward (default 1)
@@ -133,6 +134,9 @@ def load_library() -> ctypes.CDLL:
         "wc_forward_levels_host": (i32, [vp, vp, i32, up, i32, vp, ctypes.c_double, ctypes.POINTER(ctypes.c_float),
                                          vp, u64, vp, vp]),
         "wc_inverse_levels_host": (i32, [vp, vp, vp, up, i32, vp, vp]),
+        "wc_coarse_units": (i32, [up, vp, i32, up, ctypes.POINTER(u64)]),
+        "wc_inverse_coarse": (i32, [vp, vp, vp, up, i32, vp, vp, up, vp]),
+        "wc_inverse_coarse_host": (i32, [vp, vp, vp, up, i32, vp, vp, up, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -335,6 +339,16 @@ class Context:
         self._check(self._L.wc_inverse_levels(self._h, ctypes.c_void_p(d_payload), ctypes.c_void_p(d_offsets),
                                               units, n, lv.ctypes.data, ctypes.c_void_p(d_out)))
 
+    def inverse_coarse(self, d_payload: int, d_offsets: int, units, n: int, levels, reduce, out_units, d_out: int):
+        """wc_inverse_coarse: unit u at 1/2^reduce[u] resolution into out_units[u]
+        (coarse_units, or the caller's offsets with the same dims).  levels None:
+        all 1; levels and reduce: n host ints, or one value for all."""
+        lv = None if levels is None else _levels_array(levels, n)
+        rd = _levels_array(reduce, n)
+        self._check(self._L.wc_inverse_coarse(self._h, ctypes.c_void_p(d_payload), ctypes.c_void_p(d_offsets), units,
+                                              n, None if lv is None else lv.ctypes.data, rd.ctypes.data, out_units,
+                                              ctypes.c_void_p(d_out)))
+
     def decompose(self, d_cells: int, dtype: int, units, n: int, d_flat: int):
         self._check(self._L.wc_decompose(self._h, ctypes.c_void_p(d_cells), dtype, units, n,
                                          ctypes.c_void_p(d_flat)))
@@ -456,6 +470,23 @@ class Context:
                                                    None if lv is None else lv.ctypes.data, out.ctypes.data))
         return out[:extent]
 
+    def inverse_coarse_host(self, payload: np.ndarray, offsets: np.ndarray, units, n: int, reduce, out_units,
+                            extent: int, levels=None, out=None):
+        """wc_inverse_coarse_host -> float32[extent] coarse boxes at out_units'
+        offsets; levels None: each unit's L is read from its payload header."""
+        p = np.ascontiguousarray(payload, dtype=np.uint8)
+        o = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lv = None if levels is None else _levels_array(levels, n)
+        rd = _levels_array(reduce, n)
+        if out is None:
+            out = np.zeros(max(extent, 1), np.float32)
+        elif out.dtype != np.float32 or out.size < extent or not out.flags.c_contiguous:
+            raise ValueError("out: contiguous float32[>= extent]")
+        self._check(self._L.wc_inverse_coarse_host(self._h, p.ctypes.data, o.ctypes.data, units, n,
+                                                   None if lv is None else lv.ctypes.data, rd.ctypes.data, out_units,
+                                                   out.ctypes.data))
+        return out[:extent]
+
     def forward_host_units(self, boxes, units, n: int, keep: float):
         """wc_forward_host_units: unit u's cells from boxes[u] (its own host
         array, all float32 or all float64) -> (payload, offsets, kept)."""
@@ -547,6 +578,18 @@ def levels_for(nx: int, ny: int, nz: int, want: int) -> int:
     """wc_levels_for (host only): the largest L <= min(want, WC_MAX_LEVELS) with
     2^L dividing nx, ny and nz; 1 if none does or the box has no cells."""
     return int(load_library().wc_levels_for(int(nx), int(ny), int(nz), int(want)))
+
+
+def coarse_units(units, n: int, reduce):
+    """wc_coarse_units (host only): (out_units, extent) of a reduction: unit u's
+    dims >> reduce[u], packed back to back with each start rounded up to 4."""
+    rd = _levels_array(reduce, n)
+    out = (WcUnit * max(n, 1))()
+    ext = ctypes.c_uint64()
+    rc = load_library().wc_coarse_units(units, rd.ctypes.data, n, out, ctypes.byref(ext))
+    if rc:
+        raise WaveletError(rc, "wc_coarse_units: negative dims or a reduce outside 0..WC_MAX_LEVELS")
+    return out, int(ext.value)
 
 
 def payload_levels(header) -> int:

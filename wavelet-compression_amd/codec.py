@@ -185,16 +185,40 @@ def read_compressed_payload(file_path) -> bytes:
         sys.exit(1)
 
 
-def decompress_payloads(payloads: Sequence[bytes], device: int = 0) -> List[np.ndarray]:
+def _coarse_dims(payloads: Sequence[bytes], dims, coarsen) -> list:
+    """The boxes' dims >> coarsen, after the checks that need no device: coarsen
+    in 0..WC_MAX_LEVELS, no more than each payload's levels, 2^coarsen dividing
+    the dims of every box with cells (ValueError naming the payload's index)."""
+    if isinstance(coarsen, bool) or not isinstance(coarsen, (int, np.integer)) or not 0 <= coarsen <= capi.WC_MAX_LEVELS:
+        raise ValueError(f"coarsen: an integer 0..{capi.WC_MAX_LEVELS}, not {coarsen!r}")
+    r = int(coarsen)
+    for i, (p, (W, H, D)) in enumerate(zip(payloads, dims)):
+        nc = int(np.frombuffer(p[12:16], "<i4")[0])
+        L = 1 if nc >= 0 else -nc
+        if r > L:
+            raise ValueError(f"payload {i}: coarsen={r} exceeds its {L} transform level(s)")
+        if W * H * D and r and (W | H | D) & ((1 << r) - 1):
+            raise ValueError(f"payload {i} ({W}x{H}x{D}): coarsen={r} needs W, H and D divisible by {1 << r}")
+    return [(W >> r, H >> r, D >> r) for W, H, D in dims]
+
+
+def decompress_payloads(payloads: Sequence[bytes], device: int = 0, coarsen: int = 0) -> List[np.ndarray]:
     """Batched inverse path: serialized payloads -> Box3D arrays (one wc_inverse_host
     call; wc_inverse_levels_host, which reads each payload's levels from its
-    header, when some payload is a multi-level one: ncoeff < 0)."""
+    header, when some payload is a multi-level one: ncoeff < 0).
+
+    coarsen = r > 0 (not a reference parameter): every box at 1/2^r resolution,
+    shape (D >> r, H >> r, W >> r), each cell the mean of a 2^r-cube of the full
+    box up to fp32 rounding, decoded from the low-pass corner of its
+    coefficients alone (wc_inverse_coarse_host).  Works on reference-format
+    payloads (one level) with r = 1 and even dims."""
     dims = []
     multi = False
     for p in payloads:
         h = np.frombuffer(p[:20], "<i4")
         dims.append((int(h[0]), int(h[1]), int(h[2])))
         multi |= int(h[3]) < 0
+    cdims = _coarse_dims(payloads, dims, coarsen)
     units, n, extent = capi.make_units(dims)
     offsets = np.zeros(max(n, 1), np.uint64)
     cur = 4
@@ -205,7 +229,11 @@ def decompress_payloads(payloads: Sequence[bytes], device: int = 0) -> List[np.n
     for i, p in enumerate(payloads):
         o = int(offsets[i])
         buf[o:o + len(p)] = np.frombuffer(p, np.uint8)
-    if multi:
+    if coarsen:
+        out_units, extent = capi.coarse_units(units, n, int(coarsen))
+        flat = context(device).inverse_coarse_host(buf, offsets, units, n, int(coarsen), out_units, extent)
+        units, dims = out_units, cdims
+    elif multi:
         flat = context(device).inverse_levels_host(buf, offsets, units, n, extent)
     else:
         flat = context(device).inverse_host(buf, offsets, units, n, extent)
@@ -216,9 +244,11 @@ def decompress_payloads(payloads: Sequence[bytes], device: int = 0) -> List[np.n
     return out
 
 
-def decompress(file_path, time: int = 0, level: int = 0, component: int = 0, box_idx: int = 0) -> np.ndarray:
-    """src/decompressor.cpp:238-255 (only file_path is used, as in the reference)."""
-    return decompress_payloads([read_compressed_payload(file_path)])[0]
+def decompress(file_path, time: int = 0, level: int = 0, component: int = 0, box_idx: int = 0,
+               coarsen: int = 0) -> np.ndarray:
+    """src/decompressor.cpp:238-255 (only file_path is used, as in the reference).
+    coarsen (not a reference parameter): see decompress_payloads."""
+    return decompress_payloads([read_compressed_payload(file_path)], coarsen=coarsen)[0]
 
 
 def inverse_wavelet_decompose(flat, x: int, y: int, z: int) -> np.ndarray:

@@ -120,3 +120,28 @@ Box3D decompress(std::string file_path, int /*time*/, int /*level*/, int /*compo
         check(c, wc_inverse_host(c, buf.data(), &off, &u, 1, out.data()), "GPU decompress");
     return out;
 }
+
+Box3D wavelet_amd::decompress_coarse(const std::string& file_path, int reduce) {
+    flush_writes(file_path);
+    const std::string payload = xz_decompress(read_file(file_path));
+    if (payload.size() < 20) fatal("Deserialization failed: payload shorter than its header");
+    int32_t hdr[5];
+    std::memcpy(hdr, payload.data(), sizeof hdr);
+    if (hdr[0] < 0 || hdr[1] < 0 || hdr[2] < 0) fatal("Deserialization failed: negative dimensions");
+    if (reduce < 0 || reduce > WC_MAX_LEVELS)
+        fatal("decompress_coarse: reduce " + std::to_string(reduce) + " outside 0.." + std::to_string(WC_MAX_LEVELS));
+    const wc_unit u{0, hdr[0], hdr[1], hdr[2], 0};
+    const int32_t r = reduce;
+    wc_unit o;
+    uint64_t extent = 0;
+    wc_coarse_units(&u, &r, 1, &o, &extent);
+    Box3D out(o.nx, o.ny, o.nz);
+    if ((uint64_t)hdr[0] * (uint64_t)hdr[1] * (uint64_t)hdr[2] == 0) return out;
+    std::vector<uint8_t> buf(payload.size() + 8);
+    std::memcpy(buf.data() + 4, payload.data(), payload.size());
+    const uint64_t off = 4;
+    wc_ctx* c = thread_ctx();
+    // levels = NULL: the file's header tells them; a reduce beyond them is refused there
+    check(c, wc_inverse_coarse_host(c, buf.data(), &off, &u, 1, nullptr, &r, &o, out.data()), "GPU coarse decompress");
+    return out;
+}

@@ -201,7 +201,9 @@ struct LevelWork {
 };
 constexpr uint32_t kLevelKeyChunk = 8;  // flat tiles per workgroup of the key pass
 
-int upload_levels(wc_ctx* c, int n, const int32_t* levels, LevelWork* w) {
+// extra: a blob of the caller's that rides along (8-B aligned on the device, *d_extra).
+int upload_levels(wc_ctx* c, int n, const int32_t* levels, LevelWork* w, const void* extra = nullptr,
+                  size_t extra_bytes = 0, const void** d_extra = nullptr) {
     const Plan& P = c->plan;
     std::vector<uint2> hdr, key, lv[WC_MAX_LEVELS - 1];
     const uint32_t cb = level_chunk_blocks();
@@ -219,7 +221,8 @@ int upload_levels(wc_ctx* c, int n, const int32_t* levels, LevelWork* w) {
     }
     size_t items = hdr.size() + key.size();
     for (const auto& v : lv) items += v.size();
-    const size_t o_levels = sizeof(uint2) * items, in_bytes = o_levels + sizeof(int32_t) * n;
+    const size_t o_levels = sizeof(uint2) * items, o_extra = round_up(o_levels + sizeof(int32_t) * n, 8),
+                 in_bytes = extra_bytes ? o_extra + extra_bytes : o_levels + sizeof(int32_t) * n;
     int rc;
     uint8_t* pin = nullptr;
     if ((rc = pin_begin(c, in_bytes, in_bytes, &pin))) return rc;
@@ -236,6 +239,10 @@ int upload_levels(wc_ctx* c, int n, const int32_t* levels, LevelWork* w) {
     for (int i = 0; i < WC_MAX_LEVELS - 1; ++i) put(lv[i], &w->lv[i], &w->nlv[i]);
     std::memcpy(pin + o_levels, levels, sizeof(int32_t) * n);
     w->levels = (const int32_t*)(d + o_levels);
+    if (extra_bytes) {
+        std::memcpy(pin + o_extra, extra, extra_bytes);
+        *d_extra = d + o_extra;
+    }
     if ((rc = ensure(c, c->lv_side, sizeof(float) * (P.coef_extent / 8 + 64)))) return rc;
     return pin_upload(c, in_bytes);
 }
@@ -972,6 +979,118 @@ int wc_inverse_levels(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_off
     }
     c->err_check_pending = true;  // malformed payloads surface at the next wc_synchronize
     if ((rc = run_levels(c, w, false, false, bad))) return rc;
+    StageTimer t(c, WC_STAGE_INVERSE);
+    e = launch_inverse(c->stream, (const float*)c->coef.p, 0, (const UnitDev*)P.d_units.p, (const XTile*)P.d_ixtiles.p,
+                       P.ign, P.lds_inverse, P.ifast, P.lds_fast, d_out, bad);
+    return e == hipSuccess ? WC_OK : hip_fail(c, e, "inverse launch");
+}
+
+// Reduced-resolution inverse (wc_coarse.hip).  Two plans: the one of the
+// full-size units gives the pair tiles of the corner decode and their look-back
+// granules; the one of out_units (the derived units (W, H, D) >> r) places each
+// compact corner in the coefficient scratch and runs the remaining L - r levels
+// and the one-level inverse on it, as wc_inverse_levels does on full arrays.
+// Both are dense plans (WC_OPT_INVERSE_ROWS = 0) and stay in the plan cache.
+int wc_inverse_coarse(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                      const int32_t* levels, const int32_t* reduce, const wc_unit* out_units, float* d_out) {
+    if (!c) return WC_ERR_INVALID;
+    int rc;
+    if ((rc = validate_units(c, units, n))) return rc;
+    if (n == 0) return WC_OK;
+    if (!d_payload || !d_offsets || !reduce || !out_units || !d_out) return fail(c, WC_ERR_INVALID, "null buffer");
+    std::vector<int32_t> ones;
+    if (!levels) {
+        ones.assign(n, 1);
+        levels = ones.data();
+    }
+    if ((rc = validate_levels(c, units, n, levels)) || (rc = validate_coarse(c, units, n, levels, reduce, out_units)))
+        return rc;
+    if (std::all_of(reduce, reduce + n, [](int32_t r) { return r == 0; }))
+        return wc_inverse_levels(c, d_payload, d_offsets, out_units, n, levels, d_out);
+    if ((rc = check_aligned(c, d_payload, "payload")) || (rc = check_aligned(c, d_offsets, "offsets", 8)) ||
+        (rc = check_aligned(c, d_out, "out")))
+        return rc;
+    if ((rc = set_device(c))) return rc;
+    // the full units' plan: the decoder ignores their cell offsets, so the key carries none
+    std::vector<wc_unit> full(units, units + n);
+    for (wc_unit& u : full) u.cell_offset = 0;
+    const bool rows = c->opt_inv_rows;
+    c->opt_inv_rows = false;  // the plans' key holds it (wc_inverse_levels)
+    const FTile* dtiles = nullptr;
+    uint32_t ndt = 0;
+    size_t dstate = 0;
+    std::vector<CornerDesc> desc(n);
+    bool any_direct = false, any_run = false;
+    uint32_t maxt = 0;  // the batch's largest ceil(end / kFlatTile): no tile index at or past it has work
+    for (int u = 0; u < n; ++u) {
+        const wc_unit& f = units[u];
+        const wc_unit& o = out_units[u];
+        if (!((uint64_t)f.nx * f.ny * f.nz)) continue;  // no tile reads the descriptor's end
+        desc[u].end = (uint32_t)((((uint64_t)o.nx - 1) * f.ny + ((uint64_t)o.ny - 1)) * f.nz + o.nz);
+        maxt = std::max(maxt, (desc[u].end - 1) / (uint32_t)kFlatTile + 1);
+    }
+    if ((rc = get_plan(c, full.data(), n)) == WC_OK) {
+        const Plan& F = c->plan;
+        dtiles = (const FTile*)F.d_dtiles.p;  // the plan moves into the cache below: its buffers stay
+        dstate = decode_state_bytes(F);
+        // dtiles is ordered by tile index, then unit: the tiles below maxt are a prefix of it
+        for (int u = 0; u < n; ++u) {
+            desc[u].dt_begin = F.units[u].dt_begin;
+            ndt += std::min(F.units[u].ndt, maxt);
+        }
+        rc = get_plan(c, out_units, n);
+    }
+    c->opt_inv_rows = rows;
+    if (rc || (rc = ensure_scratch(c)) || (rc = ensure(c, c->state, dstate))) return rc;
+    const Plan& P = c->plan;
+    std::vector<int32_t> rest(n);  // levels left after the corner: L - r (1 for r == L, which runs nothing)
+    for (int u = 0; u < n; ++u) {
+        const wc_unit& f = units[u];
+        const wc_unit& o = out_units[u];
+        CornerDesc& d = desc[u];
+        const int L = levels[u], r = reduce[u];
+        rest[u] = std::max(1, L - r);
+        d.direct = r == L ? 1u : 0u;
+        d.dst_off = P.units[u].coef_off;
+        d.out_off = o.cell_offset;
+        d.W = f.nx;
+        d.H = f.ny;
+        d.D = f.nz;
+        d.w = (uint32_t)o.nx;
+        d.h = (uint32_t)o.ny;
+        d.d = (uint32_t)o.nz;
+        const uint64_t cells = (uint64_t)f.nx * f.ny * f.nz;
+        d.want = L >= 2 ? -L : (int32_t)cells;
+        if (!cells) continue;  // no tile reads the descriptor
+        d.dmagic = rows_magic(f.nz);
+        d.hmagic = rows_magic(f.ny);
+        any_direct |= d.direct != 0;
+        any_run |= d.direct == 0;
+    }
+    LevelWork w;
+    const void* d_desc = nullptr;
+    if ((rc = upload_levels(c, n, rest.data(), &w, desc.data(), sizeof(CornerDesc) * n, &d_desc))) return rc;
+    uint8_t* st = (uint8_t*)c->state.p;
+    hipError_t e = hipMemsetAsync(st, 0, dstate, c->stream);  // tickets and look-back status
+    if (e != hipSuccess) return hip_fail(c, e, "memset");
+    uint32_t* bad = (uint32_t*)c->npairs.p;  // per-unit "skip" words, as in wc_inverse_levels
+    {
+        StageTimer t(c, WC_STAGE_DECODE);
+        // the compact corners: positions without a pair must read as zeros
+        if (P.coef_extent && (e = hipMemsetAsync(c->coef.p, 0, sizeof(float) * P.coef_extent, c->stream)) != hipSuccess)
+            return hip_fail(c, e, "memset");
+        e = launch_decode_corner(c->stream, (const CornerDesc*)d_desc, dtiles, ndt, d_payload, d_offsets, (uint32_t*)st,
+                                 (unsigned long long*)(st + round_up(4ull * n, 8)), (float*)c->coef.p,
+                                 (uint32_t*)c->errflag.p, use_ordered(c) ? (c->opt_reverse ? 2 : 1) : 0, bad);
+        // the units with r == L: their corners are their cells
+        if (e == hipSuccess && any_direct)
+            e = launch_corner_box(c->stream, (const CornerDesc*)d_desc, (const FTile*)P.d_ftiles.p,
+                                  (uint32_t)P.ftiles.size(), (const float*)c->coef.p, d_out, bad);
+        if (e != hipSuccess) return hip_fail(c, e, "corner decode launch");
+    }
+    c->err_check_pending = true;  // malformed payloads surface at the next wc_synchronize
+    if (w.maxl >= 2 && (rc = run_levels(c, w, false, false, bad))) return rc;
+    if (!any_run) return WC_OK;  // every unit's corner was its result
     StageTimer t(c, WC_STAGE_INVERSE);
     e = launch_inverse(c->stream, (const float*)c->coef.p, 0, (const UnitDev*)P.d_units.p, (const XTile*)P.d_ixtiles.p,
                        P.ign, P.lds_inverse, P.ifast, P.lds_fast, d_out, bad);

@@ -19,6 +19,8 @@
 //   wc_levelshost.cpp host side of the multi-level mode: wc_levels_for,
 //                    wc_payload_levels, the mode's argument checks and the
 //                    _levels_host entry points
+//   wc_coarsehost.cpp host side of the reduced-resolution inverse: wc_coarse_units,
+//                    the argument checks and wc_inverse_coarse_host
 #pragma once
 
 #include "wavelet_amd.h"
@@ -77,6 +79,14 @@ hipError_t launch_level_headers(hipStream_t, const UnitDev*, const uint2* items,
 hipError_t launch_level_flat(hipStream_t, const UnitDev*, const FTile*, uint32_t ntiles, float* coef, float* flat,
                              int to_flat);
 uint32_t level_chunk_blocks();
+// wc_coarse.hip: the corner decode (over a prefix of the full plan's decode
+// tiles) into the compact corners, and the copy of the corners of the units with
+// r == L to their Box3D cells (over the derived plan's flat tiles)
+hipError_t launch_decode_corner(hipStream_t, const CornerDesc*, const FTile* dtiles, uint32_t ndt,
+                                const uint8_t* payload, const uint64_t* offsets, uint32_t* ticket,
+                                unsigned long long* status, float* corner, uint32_t* err, int ordered, uint32_t* bad);
+hipError_t launch_corner_box(hipStream_t, const CornerDesc*, const FTile* ftiles, uint32_t nft, const float* corner,
+                             float* out, const uint32_t* bad);
 
 struct DevBuf {
     void* p = nullptr;
@@ -248,6 +258,12 @@ int validate_tol(wc_ctx* c, const wc_unit* units, int n, const double* tol);
 
 // wc_levelshost.cpp
 int validate_levels(wc_ctx* c, const wc_unit* units, int n, const int32_t* levels);
+std::vector<int> level_runs(const wc_ctx* c, const wc_unit* units, int n);
+
+// wc_coarsehost.cpp
+int validate_coarse(wc_ctx* c, const wc_unit* units, int n, const int32_t* levels, const int32_t* reduce,
+                    const wc_unit* out_units);
+uint64_t rows_magic(int32_t d);
 
 // Bracket one launch with events when profiling is on.
 struct StageTimer {

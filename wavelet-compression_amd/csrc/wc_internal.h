@@ -84,6 +84,28 @@ struct FTile {
     uint32_t index;  // tile index within the unit
 };
 
+// One unit of the reduced-resolution inverse (wc_coarse.hip k_decode_corner):
+// the payload's box, the corner (w, h, d) = (W, H, D) >> r the call needs of it
+// and where the corner goes.  Built per call (the reduce is not part of a plan).
+struct CornerDesc {
+    uint64_t dst_off;   // element offset of the compact corner in the coefficient scratch (the derived unit's coef_off)
+    uint64_t out_off;   // the unit's first output cell
+    uint64_t dmagic;    // div_rows magic of D: row = floor(position / D)
+    uint64_t hmagic;    // div_rows magic of H: I = floor(row / H)
+    int32_t W, H, D;    // the payload's box
+    int32_t want;       // the header's ncoeff field: W*H*D, or -L for L >= 2
+    uint32_t w, h, d;   // the corner
+    uint32_t end;       // ((w-1)*H + (h-1))*D + d: no flat position at or past it is in the corner
+    uint32_t dt_begin;  // the unit's first look-back granule
+    uint32_t direct;    // 1: r == L, the corner is the result: k_corner_box copies it out, no pass or inverse runs
+};
+static_assert(sizeof(CornerDesc) == 72, "descriptor of 8-B members first");
+
+// Per-unit words the corner decode leaves for the launches after it (bad[u]).
+constexpr uint32_t kCornerRun = 0u;     // the level passes and the one-level inverse run
+constexpr uint32_t kCornerRefused = 1u; // the header disagrees: nothing more runs, the cells stay untouched
+constexpr uint32_t kCornerBox = 2u;     // r == L: k_corner_box writes the cells, the passes and the inverse skip
+
 // Sentinel for a unit whose flat[0] is NaN: std::max_element then returns
 // flat[0] itself (every comparison with NaN is false), so thresh is NaN.
 constexpr unsigned long long kKeyNaNFirst = ~0ull;

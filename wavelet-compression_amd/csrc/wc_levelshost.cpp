@@ -38,10 +38,6 @@ int validate_levels(wc_ctx* c, const wc_unit* units, int n, const int32_t* level
     return WC_OK;
 }
 
-}  // namespace wc
-
-namespace {
-
 // contiguous unit runs of at least opt_host_chunk cells (0: one run)
 std::vector<int> level_runs(const wc_ctx* c, const wc_unit* units, int n) {
     std::vector<int> rb{0};
@@ -58,6 +54,10 @@ std::vector<int> level_runs(const wc_ctx* c, const wc_unit* units, int n) {
     rb.push_back(n);
     return rb;
 }
+
+}  // namespace wc
+
+namespace {
 
 // the span of cells the units [a, a + m) own
 void cell_span(const wc_unit* units, int a, int m, uint64_t& lo, uint64_t& hi) {
