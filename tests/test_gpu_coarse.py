@@ -3,7 +3,9 @@ wc_inverse_coarse_host, codec.decompress(coarsen=), the C++ mirror's
 decompress_coarse) against the CPU restatement coarse_ref.py.
 
 Bar: bit for bit on cells.  Every element of the output buffer that no unit
-owns must keep its sentinel.  Finite data only.
+owns must keep its sentinel.  The data here is finite; payloads of NaN, +-inf,
+-0 and subnormal cells at random shapes and reductions are in
+tests/test_gpu_modes_fuzz.py.
 
 Shapes, the smallest that reach each path: 2^3 L1 r1 (a corner of one
 coefficient), 4^3 L2, 8^3 L3, 16^3 L4 at every r (the last level is one 2x2x2

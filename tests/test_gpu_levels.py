@@ -7,7 +7,9 @@ Bar: bit for bit.  Flat coefficient arrays, payload bytes, kept counts and
 slot offsets for the keep rule and for an explicit threshold, reconstructed
 cells; the host variants equal the device calls; all-ones levels equal
 wc_forward / wc_inverse; bad arguments and mismatching headers are refused
-with their codes and touch nothing they promise not to.  Finite data only.
+with their codes and touch nothing they promise not to.  The data here is
+finite; NaN, +-inf, -0 and subnormal cells, random shapes and the look-back
+option sets are in tests/test_gpu_modes_fuzz.py.
 
 Shapes, the smallest that reach each path: 4^3 L2, 8^3 L3, 16^3 L4 (the last
 level is one 2x2x2 block; odd block counts along K take the scalar pass),
