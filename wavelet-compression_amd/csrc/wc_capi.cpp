@@ -692,6 +692,24 @@ int wc_decompose(wc_ctx* c, const void* d_cells, int dtype, const wc_unit* units
 
 namespace {
 
+// Per-call state of the pair-tile scans of a decode (wc_pairscan.h): ticket[n] |
+// status[decode tiles] in c->state, `bytes` in all (decode_state_bytes of the
+// plan whose decode tiles run), zeroed here; `ordered`: the kernels' tile-index
+// argument.  dense: some unit's tiles look back over zeroed granules; without
+// one the ordered form needs no state (the row index's granules carry the
+// call's epoch) and the clear is skipped.
+struct DecodeState {
+    uint32_t* ticket;
+    unsigned long long* status;
+    int ordered;  // 0: tickets, 1: plan order, 2: reversed (WC_OPT_REVERSE_TILES)
+};
+hipError_t decode_state(wc_ctx* c, int n, size_t bytes, bool dense, DecodeState* s) {
+    uint8_t* st = (uint8_t*)c->state.p;
+    *s = {(uint32_t*)st, (unsigned long long*)(st + round_up(4ull * n, 8)),
+          use_ordered(c) ? (c->opt_reverse ? 2 : 1) : 0};
+    return dense || !s->ordered ? hipMemsetAsync(st, 0, bytes, c->stream) : hipSuccess;
+}
+
 // wc_inverse, and with orig != null also calc_rmse_per_box fused into the
 // row-indexed inverse (every unit row-indexed; the caller checks).
 // user_rows (wc_inverse_rows): the caller's row index of these payloads, as
@@ -702,14 +720,9 @@ int inverse_impl(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets,
     Plan& P = c->plan;
     int rc = WC_OK;
     hipError_t e = hipSuccess;
-    // per-call state of the dense decode and of the ticket form: ticket[n] |
-    // status[decode tiles] (zeroed).  The row index needs none: its granules
-    // carry the call's epoch.  The dense coefficient scratch is fully written
-    // by the decode (no memset).
-    uint8_t* st = (uint8_t*)c->state.p;
-    const bool ord = use_ordered(c);  // once: the clear below and the launch must agree
-    if ((!P.dtiles.empty() || !ord) &&
-        (e = hipMemsetAsync(st, 0, decode_state_bytes(P), c->stream)) != hipSuccess)
+    // The dense coefficient scratch is fully written by the decode (no memset).
+    DecodeState ds;  // once: the clear and the launches must agree on the form
+    if ((e = decode_state(c, n, decode_state_bytes(P), !P.dtiles.empty(), &ds)) != hipSuccess)
         return hip_fail(c, e, "memset");
     c->epoch = (c->epoch + 1) & kEpochMask;
     if (c->epoch == 0) {  // wrapped: granules of 2^30 calls ago could look current
@@ -733,9 +746,8 @@ int inverse_impl(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets,
         return launch_decode(s, (const UnitDev*)P.d_units.p, (const FTile*)P.d_dtiles.p,
                              dense ? (uint32_t)P.dtiles.size() : 0u, (const FTile*)P.d_rdtiles.p + (dense ? 0 : P.ig_rd[g]),
                              dense ? 0u : P.ig_rd[g + 1] - P.ig_rd[g], (unsigned long long*)c->istate.p, c->epoch,
-                             d_payload, d_offsets, (uint32_t*)st, (unsigned long long*)(st + round_up(4ull * n, 8)),
-                             (float*)c->coef.p, (uint2*)c->rowinfo.p, (uint32_t*)c->errflag.p, ord ? (c->opt_reverse ? 2 : 1) : 0,
-                             (uint32_t*)c->npairs.p);
+                             d_payload, d_offsets, ds.ticket, ds.status, (float*)c->coef.p, (uint2*)c->rowinfo.p,
+                             (uint32_t*)c->errflag.p, ds.ordered, (uint32_t*)c->npairs.p);
     };
     if (piped) {
         // K5 of group g + 1 on the context stream beside K6r of group g on the
@@ -963,8 +975,8 @@ int wc_inverse_levels(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_off
     LevelWork w;
     if ((rc = upload_levels(c, n, levels, &w))) return rc;
     const Plan& P = c->plan;
-    uint8_t* st = (uint8_t*)c->state.p;
-    hipError_t e = hipMemsetAsync(st, 0, decode_state_bytes(P), c->stream);  // tickets and look-back status
+    DecodeState ds;
+    hipError_t e = decode_state(c, n, decode_state_bytes(P), true, &ds);
     if (e != hipSuccess) return hip_fail(c, e, "memset");
     // per-unit "header disagrees" words, written by each unit's first decode tile (a unit
     // without cells has neither decode nor inverse tiles); npairs is free: no unit is row-indexed
@@ -972,9 +984,8 @@ int wc_inverse_levels(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_off
     {
         StageTimer t(c, WC_STAGE_DECODE);
         e = launch_decode(c->stream, (const UnitDev*)P.d_units.p, (const FTile*)P.d_dtiles.p, (uint32_t)P.dtiles.size(),
-                          nullptr, 0u, nullptr, 0u, d_payload, d_offsets, (uint32_t*)st,
-                          (unsigned long long*)(st + round_up(4ull * n, 8)), (float*)c->coef.p, nullptr,
-                          (uint32_t*)c->errflag.p, use_ordered(c) ? (c->opt_reverse ? 2 : 1) : 0, bad, w.levels);
+                          nullptr, 0u, nullptr, 0u, d_payload, d_offsets, ds.ticket, ds.status, (float*)c->coef.p, nullptr,
+                          (uint32_t*)c->errflag.p, ds.ordered, bad, w.levels);
         if (e != hipSuccess) return hip_fail(c, e, "decode launch");
     }
     c->err_check_pending = true;  // malformed payloads surface at the next wc_synchronize
@@ -1070,8 +1081,8 @@ int wc_inverse_coarse(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_off
     LevelWork w;
     const void* d_desc = nullptr;
     if ((rc = upload_levels(c, n, rest.data(), &w, desc.data(), sizeof(CornerDesc) * n, &d_desc))) return rc;
-    uint8_t* st = (uint8_t*)c->state.p;
-    hipError_t e = hipMemsetAsync(st, 0, dstate, c->stream);  // tickets and look-back status
+    DecodeState ds;
+    hipError_t e = decode_state(c, n, dstate, true, &ds);
     if (e != hipSuccess) return hip_fail(c, e, "memset");
     uint32_t* bad = (uint32_t*)c->npairs.p;  // per-unit "skip" words, as in wc_inverse_levels
     {
@@ -1079,9 +1090,8 @@ int wc_inverse_coarse(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_off
         // the compact corners: positions without a pair must read as zeros
         if (P.coef_extent && (e = hipMemsetAsync(c->coef.p, 0, sizeof(float) * P.coef_extent, c->stream)) != hipSuccess)
             return hip_fail(c, e, "memset");
-        e = launch_decode_corner(c->stream, (const CornerDesc*)d_desc, dtiles, ndt, d_payload, d_offsets, (uint32_t*)st,
-                                 (unsigned long long*)(st + round_up(4ull * n, 8)), (float*)c->coef.p,
-                                 (uint32_t*)c->errflag.p, use_ordered(c) ? (c->opt_reverse ? 2 : 1) : 0, bad);
+        e = launch_decode_corner(c->stream, (const CornerDesc*)d_desc, dtiles, ndt, d_payload, d_offsets, ds.ticket,
+                                 ds.status, (float*)c->coef.p, (uint32_t*)c->errflag.p, ds.ordered, bad);
         // the units with r == L: their corners are their cells
         if (e == hipSuccess && any_direct)
             e = launch_corner_box(c->stream, (const CornerDesc*)d_desc, (const FTile*)P.d_ftiles.p,

@@ -24,74 +24,31 @@
 //                    one-level C2 payloads took 0.55 ms against 0.17 ms into
 //                    the compact order.)
 //
-// k_decode_corner keeps k_decode's structure (wc_inverse.hip): pair tile t
-// (kFlatTile pairs; wave w, round r, lane l holds pair t*kFlatTile + w*1024 +
-// r*64 + l), in-wave DPP scans of run + 1, the sum over the unit's earlier
-// tiles from a decoupled look-back over zeroed 62-bit granules, the tile index
-// from the launch order or a per-unit ticket (WC_OPT_ORDERED).  Sums are
-// 32-bit and saturate, as in k_rowindex: every position this kernel acts on is
-// below end <= W*H*D < 2^31, and a saturated sum is past it like the exact one.
-// A negative run (malformed, kErrNegativeRun) counts as run 0, so positions
-// never decrease: pair k lands at a position >= k.
-//
-// Which tiles run, and why no look-back waits on a tile that has left:
-//   - The unit's tiles are [0, T), T = min(pair tiles of the payload,
-//     ceil(end / kFlatTile)): a tile t >= T has its first pair index
-//     t*kFlatTile >= end (or no pair at all), so every pair of it and of every
-//     later tile lies at or past end.  Blocks whose plan index is >= T exit
-//     after the header, before any atomic, exactly as k_decode's blocks past
-//     the payload's pair tiles do: in the ordered forms t is the plan index (or
-//     T - 1 - index), in the ticket form exactly T blocks draw the tickets
-//     0..T-1.  A look-back of tile t < T reads only granules of tiles < t < T,
-//     all of which run; none of them belongs to a block that has left.
-//   - A tile t < T whose exclusive prefix turns out >= end still publishes its
-//     inclusive sum, then skips the scatter: tiles after it (still < T) may be
-//     waiting on its granule.
-//   - No further skipping.  A tile that cannot know its prefix cannot know that
-//     it is past the corner, and leaving before publishing would make its
-//     successors derive its sum from its pairs: more work, not less.
-// The wait itself is lookback_sum62's: after its bound a wave derives the
-// predecessor's sum from that tile's pairs and publishes it (DESIGN.md §Forward
-// progress), so no wait depends on which workgroups are resident.
+// k_decode_corner runs the decoders' shared pair-tile scan (wc_pairscan.h
+// PairScan, which also owns the rule for which tiles run and why no look-back
+// waits on a tile that has left) over zeroed 62-bit granules.  Sums are Sat32,
+// as in k_rowindex: every position this kernel acts on is below end <= W*H*D <
+// 2^31, and a saturated sum is past it like the exact one; a negative run counts
+// as run 0, so pair k lands at a position >= k.  The unit's tiles are [0, T),
+// T = min(pair tiles of the payload, ceil(end / kFlatTile)); a tile t < T whose
+// exclusive prefix turns out >= end has published its inclusive sum by then and
+// skips the scatter.
 //
 // Bounds: a pair is stored only if its position p < end and its (I, J, K) from
 // p lies inside (w, h, d), so every store is inside the unit's w*h*d elements
 // at dst_off, whatever the payload holds; pair loads are bounded by the header's
 // pair count, as in k_decode.
-#include "wc_device.h"
+#include "wc_pairscan.h"
 
 namespace wc {
-
-constexpr int kCornerRounds = kFlatTile / kThreads;  // 16 pairs per lane
-
-__device__ __forceinline__ uint32_t sat_add32(uint32_t a, uint32_t b) { return __builtin_elementwise_add_sat(a, b); }
-
-// wave_incl_sum32 with saturating adds (wc_inverse.hip wave_incl_sum32_sat)
-__device__ __forceinline__ uint32_t wave_incl_sum32_sat_c(uint32_t v) {
-    v = sat_add32(v, __builtin_amdgcn_update_dpp(0u, v, 0x111, 0xf, 0xf, false));
-    v = sat_add32(v, __builtin_amdgcn_update_dpp(0u, v, 0x112, 0xf, 0xf, false));
-    v = sat_add32(v, __builtin_amdgcn_update_dpp(0u, v, 0x114, 0xf, 0xf, false));
-    v = sat_add32(v, __builtin_amdgcn_update_dpp(0u, v, 0x118, 0xf, 0xf, false));
-    v = sat_add32(v, __builtin_amdgcn_update_dpp(0u, v, 0x142, 0xa, 0xf, false));
-    v = sat_add32(v, __builtin_amdgcn_update_dpp(0u, v, 0x143, 0xc, 0xf, false));
-    return v;
-}
-
-// The header must carry the unit's box and its levels (ncoeff = -L for L >= 2)
-// and nrle >= 0, as read_header of wc_inverse.hip asks for wc_inverse_levels.
-__device__ __forceinline__ bool corner_header(const CornerDesc& C, const uint8_t* __restrict__ ph, int32_t& nrle) {
-    const int32_t* h = reinterpret_cast<const int32_t*>(ph);
-    nrle = h[4];
-    return h[0] == C.W && h[1] == C.H && h[2] == C.D && h[3] == C.want && nrle >= 0;
-}
 
 // tiles: the decode tiles of the plan of the FULL units (interleaved by tile
 // index across units; a prefix of that list: every tile index below the
 // batch's largest ceil(end / kFlatTile)).  bad[u] (written by the unit's first
-// tile, read by later launches): kCornerRefused = the header disagrees
+// tile, read by later launches): kUnitRefused = the header disagrees
 // (kErrHeader; nothing past the header is read, no cell is written, every later
-// launch skips the unit); kCornerBox = r == L (k_corner_box writes the cells, the
-// level passes and the inverse skip the unit); kCornerRun otherwise.
+// launch skips the unit); kUnitBox = r == L (k_corner_box writes the cells, the
+// level passes and the inverse skip the unit); kUnitRun otherwise.
 __global__ __launch_bounds__(kThreads) void k_decode_corner(const CornerDesc* __restrict__ desc,
                                                           const FTile* __restrict__ tiles,
                                                           const uint8_t* __restrict__ payload,
@@ -101,8 +58,9 @@ __global__ __launch_bounds__(kThreads) void k_decode_corner(const CornerDesc* __
                                                           float* __restrict__ corner,
                                                           uint32_t* __restrict__ err, int ordered,
                                                           uint32_t* __restrict__ bad) {
-    __shared__ uint32_t s_w[4];
-    __shared__ unsigned long long s_x[2];
+    using Scan = PairScan<Sat32, Granule62, kFlatTile, LoadPairs>;
+    __shared__ Scan::T s_w[4];
+    __shared__ Scan::V s_x[2];
     const int tid = threadIdx.x, l = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const FTile ft = tiles[blockIdx.x];
@@ -110,9 +68,9 @@ __global__ __launch_bounds__(kThreads) void k_decode_corner(const CornerDesc* __
     const CornerDesc C = desc[u];
     const uint8_t* ph = payload + offsets[u];
     int32_t nrle;
-    const bool hok = corner_header(C, ph, nrle);
+    const bool hok = header_ok(C.W, C.H, C.D, C.want, ph, nrle);
     if (ft.index == 0 && tid == 0) {
-        bad[u] = !hok ? kCornerRefused : C.direct ? kCornerBox : kCornerRun;
+        bad[u] = !hok ? kUnitRefused : C.direct ? kUnitBox : kUnitRun;
         if (!hok) atomicOr(err, kErrHeader);
     }
     if (!hok) return;  // uniform
@@ -120,76 +78,28 @@ __global__ __launch_bounds__(kThreads) void k_decode_corner(const CornerDesc* __
     const uint32_t ptiles = n ? (n - 1u) / (uint32_t)kFlatTile + 1u : 1u;
     const uint32_t T = min(ptiles, (C.end - 1u) / (uint32_t)kFlatTile + 1u);  // end >= 1: the unit has cells
     if (ft.index >= T) return;  // uniform; before any atomic
-    uint32_t t = ordered == 2 ? T - 1u - ft.index : ft.index;  // 2: reversed (test hook)
-    if (!ordered) {
-        if (tid == 0) s_x[0] = atomicAdd(ticket + u, 1u);
-        __syncthreads();
-        t = (uint32_t)s_x[0];
-    }
+    const uint32_t t = Scan::tile_index(ft.index, T, ordered, ticket + u, s_x);
 
-    // 1. this lane's pairs and the saturating in-wave inclusive sums of (run + 1)
-    const uint2* __restrict__ pr = reinterpret_cast<const uint2*>(ph + 20);
-    const uint32_t kw = t * (uint32_t)kFlatTile + (uint32_t)w * (kFlatTile / 4);
-    uint2 q[kCornerRounds];
+    // 1. this lane's pairs and the saturating in-wave inclusive sums of (run + 1);
+    // 2. the sum over the unit's earlier tiles
+    const uint32_t* __restrict__ runs = reinterpret_cast<const uint32_t*>(ph + 20);
+    const uint32_t kw = Scan::wave_first(t, w);
+    uint2 q[Scan::kRounds];
 #pragma unroll
-    for (int r = 0; r < kCornerRounds; ++r) {
-        const uint32_t k = kw + r * 64 + l;
-        q[r] = k < n ? pr[k] : make_uint2(0u, 0u);
-    }
-    uint32_t incl[kCornerRounds];
-    uint32_t wsum = 0;
-    bool neg = false;
+    for (int r = 0; r < Scan::kRounds; ++r) q[r] = Scan::load(runs, kw + r * 64 + l, n);
+    uint32_t incl[Scan::kRounds];
+    Scan::WaveSums ws;
 #pragma unroll
-    for (int r = 0; r < kCornerRounds; ++r) {
-        const uint32_t k = kw + r * 64 + l;
-        const int32_t run = (int32_t)q[r].x;
-        neg |= k < n && run < 0;
-        const uint32_t x = k < n ? (run < 0 ? 1u : (uint32_t)run + 1u) : 0u;
-        const uint32_t s = wave_incl_sum32_sat_c(x);
-        incl[r] = sat_add32(wsum, s);
-        wsum = sat_add32(wsum, __builtin_amdgcn_readlane(s, 63));
-    }
-    if (neg) atomicOr(err, kErrNegativeRun);
-    if (l == 0) s_w[w] = wsum;
-    __syncthreads();
-    uint32_t wexcl = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        wexcl = i < w ? sat_add32(wexcl, s_w[i]) : wexcl;
-        tot = sat_add32(tot, s_w[i]);
-    }
-
-    // 2. the sum over the unit's earlier tiles: look-back
-    if (w == 0) {
-        unsigned long long* st = status + C.dt_begin;
-        unsigned long long excl = 0;
-        if (t == 0) {
-            if (l == 0) st_rlx(st, kFlagIncl | (unsigned long long)tot);
-        } else {
-            if (l == 0) st_rlx(st + t, kFlagAgg | (unsigned long long)tot);
-            // a predecessor tile unpublished after the wait bound: its sum from its pairs
-            excl = lookback_sum62(st, (int64_t)t, l, err, [&](int64_t j) -> unsigned long long {
-                const uint32_t k0 = (uint32_t)j * (uint32_t)kFlatTile, k1 = min(k0 + (uint32_t)kFlatTile, n);
-                uint32_t a = 0;
-                for (uint32_t k = k0 + (uint32_t)l; k < k1; k += 64) {
-                    const int32_t run = (int32_t)pr[k].x;
-                    a = sat_add32(a, run < 0 ? 1u : (uint32_t)run + 1u);
-                }
-                return (unsigned long long)__builtin_amdgcn_readlane(wave_incl_sum32_sat_c(a), 63);
-            });
-            if (l == 0) st_rlx(st + t, kFlagIncl | ((excl + tot) & kMask62));
-        }
-        if (l == 0) s_x[1] = excl;
-    }
-    __syncthreads();
-    const uint64_t A = s_x[1];  // positions before this tile's first pair
+    for (int r = 0; r < Scan::kRounds; ++r) incl[r] = ws.round(q[r], kw + r * 64 + l, n);
+    const Scan::Prefix P = Scan::prefix(ws.finish(err), t, n, runs, status + C.dt_begin, Granule62{}, err, s_w, s_x, w, l);
+    const uint64_t A = P.excl;  // positions before this tile's first pair
     if (A >= (uint64_t)C.end) return;  // uniform: the whole tile is past the corner (its sum is published)
 
     // 3. the pairs inside the corner, to their compact places
     float* __restrict__ dst = corner + C.dst_off;
-    const uint64_t base = A + wexcl;  // + incl[r] - 1: position of the lane's pair in round r
+    const uint64_t base = A + P.wexcl;  // + incl[r] - 1: position of the lane's pair in round r
 #pragma unroll
-    for (int r = 0; r < kCornerRounds; ++r) {
+    for (int r = 0; r < Scan::kRounds; ++r) {
         const uint32_t k = kw + r * 64 + l;
         const uint64_t p64 = base + incl[r] - 1u;  // incl >= 1 where k < n
         if (k >= n || p64 >= (uint64_t)C.end) continue;
@@ -214,7 +124,7 @@ __global__ __launch_bounds__(kThreads) void k_corner_box(const CornerDesc* __res
                                                        const uint32_t* __restrict__ bad) {
     __shared__ float tile[kBoxTile][kBoxTile + 1];
     const FTile ft = tiles[blockIdx.x];
-    if (bad[ft.unit] != kCornerBox) return;  // uniform
+    if (bad[ft.unit] != kUnitBox) return;  // uniform
     const CornerDesc C = desc[ft.unit];
     const uint32_t w = C.w, h = C.h, d = C.d;
     const uint32_t ti = (w + kBoxTile - 1) / kBoxTile, tk = (d + kBoxTile - 1) / kBoxTile;

@@ -27,7 +27,7 @@ __device__ __forceinline__ T wave_sum(T v) {
 }
 
 // Wave reductions on DPP lane moves (row_shr 1/2/4/8 inside 16-lane rows,
-// then row_bcast 15 / 31 across them, as wave_incl_sum below): lane 63 ends
+// then row_bcast 15 / 31 across them, as wave_incl_sum32 below): lane 63 ends
 // with the reduction over all 64 lanes, returned uniformly by readlane.  A
 // chain of six VALU ops instead of six LDS-crossbar bpermutes (__shfl_xor).
 // Lanes whose DPP source is out of range read 0, the identity of the unsigned
@@ -238,8 +238,42 @@ __device__ __forceinline__ bool spin_wait(uint32_t& spins, const uint32_t* err) 
     return false;
 }
 
+// Granule forms of a look-back: V, the sum a tile hands on; encode(flag, sum);
+// decode(raw), the granule as this call sees it (0: unpublished); value(v), its
+// sum; finish(excl), the look-back's result; add, the inclusive prefix.
+//   Granule62       flag (2 bits) | 62-bit sum (wrapping), zeroed before each call.
+//   GranuleEpoch32  flag (2 bits) | epoch (30 bits) | 32-bit saturated sum.  A
+//                   granule of another epoch (an earlier call) reads as
+//                   unpublished, so a buffer of such granules needs zeroing only
+//                   once, when it is allocated.
+struct Granule62 {
+    using V = unsigned long long;
+    __device__ __forceinline__ unsigned long long encode(unsigned long long flag, V sum) const {
+        return flag | (sum & kMask62);
+    }
+    __device__ __forceinline__ unsigned long long decode(unsigned long long raw) const { return raw; }
+    static __device__ __forceinline__ unsigned long long value(unsigned long long v) { return v & kMask62; }
+    static __device__ __forceinline__ V finish(unsigned long long excl) { return excl & kMask62; }
+    static __device__ __forceinline__ V add(V a, V b) { return a + b; }
+};
+struct GranuleEpoch32 {
+    using V = uint32_t;
+    uint32_t ep;  // the call's epoch & kEpochMask
+    __device__ __forceinline__ unsigned long long encode(unsigned long long flag, V sum) const {
+        return flag | ((unsigned long long)ep << 32) | sum;
+    }
+    __device__ __forceinline__ unsigned long long decode(unsigned long long raw) const {
+        return (uint32_t)(raw >> 32 & kEpochMask) != ep ? 0ull : raw;  // an earlier call's: unpublished
+    }
+    static __device__ __forceinline__ unsigned long long value(unsigned long long v) { return v & 0xffffffffull; }
+    static __device__ __forceinline__ V finish(unsigned long long excl) {
+        return excl > 0xffffffffull ? 0xffffffffu : (V)excl;
+    }
+    static __device__ __forceinline__ V add(V a, V b) { return __builtin_elementwise_add_sat(a, b); }
+};
+
 // Decoupled look-back (one wave): exclusive prefix of tile t from granules
-// st[0..t) of 62-bit sums.  A window of the 64 nearest predecessors (lane l =
+// st[0..t) of form G.  A window of the 64 nearest predecessors (lane l =
 // tile pos - l; indices below 0 read as an inclusive 0) is summed up to the
 // nearest inclusive granule once every lane before it has published; a run
 // of published aggregates before the first unpublished tile is summed and
@@ -247,78 +281,40 @@ __device__ __forceinline__ bool spin_wait(uint32_t& spins, const uint32_t* err) 
 // bound is summed from agg(tile) (a wave-uniform call by the whole wave: the
 // tile's aggregate derived from its inputs, as its own block would publish it),
 // and published there as an aggregate granule.
-template <class Agg>
-__device__ __forceinline__ unsigned long long lookback_sum62(unsigned long long* st, int64_t t, int l,
-                                                             const uint32_t* err, Agg agg) {
+template <class G, class Agg>
+__device__ __forceinline__ typename G::V lookback_sum(unsigned long long* st, int64_t t, int l, const uint32_t* err,
+                                                      G g, Agg agg) {
     unsigned long long excl = 0;
     int64_t pos = t - 1;
     for (uint32_t spins = 0;;) {
         const int64_t idx = pos - l;
-        const unsigned long long v = idx >= 0 ? ld_rlx(st + idx) : kFlagIncl;
+        const unsigned long long raw = idx >= 0 ? ld_rlx(st + idx) : g.encode(kFlagIncl, 0);
+        const unsigned long long v = g.decode(raw);
         const unsigned long long incl = __ballot((v >> 62) == 2);
         const unsigned long long zero = __ballot((v >> 62) == 0);
         const int kI = incl ? __ffsll((long long)incl) - 1 : 64;
         const int kZ = zero ? __ffsll((long long)zero) - 1 : 64;
         const int take = kI < kZ ? kI + 1 : kZ;  // lanes [0, take) are summed
         if (take > 0) {
-            excl += wave_sum(l < take ? (v & kMask62) : 0ull);
+            excl += wave_sum(l < take ? G::value(v) : 0ull);
             spins = 0;  // progress: a later unpublished tile gets a full wait
         }
         if (kI < kZ) break;
         pos -= take;
         if (take == 0 && spin_wait(spins, err)) {  // tile pos (lane 0's): derived here
-            const unsigned long long a = agg(pos) & kMask62;
-            if (l == 0) publish_derived(st + pos, v, kFlagAgg | a);
+            const unsigned long long a = G::value(agg(pos));
+            if (l == 0) publish_derived(st + pos, raw, g.encode(kFlagAgg, (typename G::V)a));
             excl += a;
             --pos;
         }
     }
-    return excl & kMask62;
+    return G::finish(excl);
 }
 
-// Epoch-tagged granules: flag (2 bits) | epoch (30 bits) | 32-bit saturated
-// sum.  A granule of another epoch (an earlier call) reads as unpublished, so
-// a buffer of such granules needs zeroing only once, when it is allocated.
-__device__ __forceinline__ unsigned long long granule_e(unsigned long long flag, uint32_t epoch, uint32_t sum) {
-    return flag | ((unsigned long long)(epoch & kEpochMask) << 32) | sum;
-}
-
-// lookback_sum62 over epoch-tagged granules; the result saturates at 2^32 - 1
-// (agg: a tile's saturated 32-bit sum).
-template <class Agg>
-__device__ __forceinline__ uint32_t lookback_sum32e(unsigned long long* st, int64_t t, int l,
-                                                    const uint32_t* err, uint32_t epoch, Agg agg) {
-    unsigned long long excl = 0;
-    int64_t pos = t - 1;
-    const uint32_t ep = epoch & kEpochMask;
-    for (uint32_t spins = 0;;) {
-        const int64_t idx = pos - l;
-        const unsigned long long raw = idx >= 0 ? ld_rlx(st + idx) : granule_e(kFlagIncl, ep, 0u);
-        const unsigned long long v = (uint32_t)(raw >> 32 & kEpochMask) != ep ? 0ull : raw;  // earlier call's: unpublished
-        const unsigned long long incl = __ballot((v >> 62) == 2);
-        const unsigned long long zero = __ballot((v >> 62) == 0);
-        const int kI = incl ? __ffsll((long long)incl) - 1 : 64;
-        const int kZ = zero ? __ffsll((long long)zero) - 1 : 64;
-        const int take = kI < kZ ? kI + 1 : kZ;  // lanes [0, take) are summed
-        if (take > 0) {
-            excl += wave_sum(l < take ? (v & 0xffffffffull) : 0ull);
-            spins = 0;
-        }
-        if (kI < kZ) break;
-        pos -= take;
-        if (take == 0 && spin_wait(spins, err)) {  // tile pos (lane 0's): derived here, published
-            const uint32_t a = agg(pos);
-            if (l == 0) publish_derived(st + pos, raw, granule_e(kFlagAgg, ep, a));
-            excl += a;
-            --pos;
-        }
-    }
-    return excl > 0xffffffffull ? 0xffffffffu : (uint32_t)excl;
-}
-
-// Wave-wide inclusive sum (64 lanes) on DPP lane moves, GFX9 pattern:
+// Wave-wide inclusive sums (64 lanes) on DPP lane moves, GFX9 pattern:
 // row_shr 1/2/4/8 within 16-lane rows, then row_bcast:15 and row_bcast:31
 // carry into the next rows.  Lanes whose source is out of range read 0.
+// (The 64-bit sum is k_decode's alone: wc_pairscan.h Exact64::wave_incl.)
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ uint64_t dpp_u64(uint64_t v) {
     const uint32_t lo = __builtin_amdgcn_update_dpp(0u, (uint32_t)v, CTRL, ROW_MASK, 0xf, false);
@@ -326,18 +322,6 @@ __device__ __forceinline__ uint64_t dpp_u64(uint64_t v) {
     return ((uint64_t)hi << 32) | lo;
 }
 
-__device__ __forceinline__ uint64_t wave_incl_sum(uint64_t v) {
-    v += dpp_u64<0x111, 0xf>(v);  // row_shr:1
-    v += dpp_u64<0x112, 0xf>(v);  // row_shr:2
-    v += dpp_u64<0x114, 0xf>(v);  // row_shr:4
-    v += dpp_u64<0x118, 0xf>(v);  // row_shr:8
-    v += dpp_u64<0x142, 0xa>(v);  // row_bcast:15 -> rows 1, 3
-    v += dpp_u64<0x143, 0xc>(v);  // row_bcast:31 -> rows 2, 3
-    return v;
-}
-
-// Wave-wide inclusive sum of 32-bit values on DPP lane moves (wave_incl_sum's
-// pattern); lanes whose source is out of range read 0.
 __device__ __forceinline__ uint32_t wave_incl_sum32(uint32_t v) {
     v += __builtin_amdgcn_update_dpp(0u, v, 0x111, 0xf, 0xf, false);  // row_shr:1
     v += __builtin_amdgcn_update_dpp(0u, v, 0x112, 0xf, 0xf, false);  // row_shr:2

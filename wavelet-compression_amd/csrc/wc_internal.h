@@ -101,10 +101,12 @@ struct CornerDesc {
 };
 static_assert(sizeof(CornerDesc) == 72, "descriptor of 8-B members first");
 
-// Per-unit words the corner decode leaves for the launches after it (bad[u]).
-constexpr uint32_t kCornerRun = 0u;     // the level passes and the one-level inverse run
-constexpr uint32_t kCornerRefused = 1u; // the header disagrees: nothing more runs, the cells stay untouched
-constexpr uint32_t kCornerBox = 2u;     // r == L: k_corner_box writes the cells, the passes and the inverse skip
+// Per-unit skip words (bad[u]) that k_decode<true> and k_decode_corner leave for
+// the launches after them: the level passes and k_inverse{,_fast}<true> skip a
+// unit unless its word is kUnitRun.
+constexpr uint32_t kUnitRun = 0u;      // the level passes and the one-level inverse run
+constexpr uint32_t kUnitRefused = 1u;  // the header disagrees: nothing more runs, the cells stay untouched
+constexpr uint32_t kUnitBox = 2u;      // wc_inverse_coarse, r == L: k_corner_box writes the cells, the rest skip
 
 // Sentinel for a unit whose flat[0] is NaN: std::max_element then returns
 // flat[0] itself (every comparison with NaN is false), so thresh is NaN.
@@ -114,7 +116,7 @@ constexpr unsigned long long kKeyNaNFirst = ~0ull;
 constexpr uint32_t kErrHeader = 1u;      // payload header disagrees with the unit
 constexpr uint32_t kErrNegativeRun = 2u; // a run length < 0 (reference: UB)
 
-constexpr uint32_t kEpochMask = 0x3fffffffu;  // epoch bits of a look-back granule (wc_device.h granule_e)
+constexpr uint32_t kEpochMask = 0x3fffffffu;  // epoch bits of a look-back granule (wc_device.h GranuleEpoch32)
 
 #ifndef WC_EMIT_EW
 #define WC_EMIT_EW 4  // waves per emit block of the small-unit launch (2048 coefficients per wave)

@@ -7,6 +7,7 @@
 //   K7   k_rmse_*: per-unit RMSE                      src/calc-loss.cpp:12-43
 // The inverse pair `avg +/- diff` is evaluated in double and stored as float
 // by the reference; a float add is bit-identical (53 >= 2*24 + 2).
+#include "wc_pairscan.h"
 #include "wc_xform.h"
 
 #include <algorithm>
@@ -18,10 +19,9 @@ namespace wc {
 // p_k = (sum of run + 1 over pairs <= k) - 1 while that is < ncoeff, which is
 // rle_decode's `idx += run; if (idx < total) out[idx++] = val`; every later
 // pair is dropped.  Pair tile t (kFlatTile pairs) gets the sum over the unit's
-// earlier tiles from a decoupled look-back (tile index from the launch order
-// or a per-unit ticket, WC_OPT_ORDERED); blocks past the payload's last pair
-// tile exit.  Pairs are loaded coalesced: wave w, round r, lane l holds pair
-// w*1024 + r*64 + l of the tile; positions come from wave scans of run + 1.
+// earlier tiles from the shared pair-tile scan (wc_pairscan.h PairScan: tile
+// index, coalesced loads, wave scans of run + 1, look-back, and the rule for
+// which tiles run).
 //
 // Two forms:
 //   k_rowindex  row-indexed units (U.rix, the even-dims fast shapes): writes
@@ -38,49 +38,13 @@ namespace wc {
 //               (the unit's last tile: through ncoeff - 1) and writes every
 //               element of it — zeros between pairs — through LDS in
 //               kDecChunk-element rounds (no memset of the scratch).
-constexpr int kDecRounds = kFlatTile / kThreads;  // 16 pairs per lane
-constexpr int kDecChunk = 4096;                   // floats per write round (16 KB of LDS)
-
-// Header check: the dims and ncoeff must be the unit's and nrle >= 0.  More
-// pairs than coefficients are accepted: rle_decode drops every pair whose
-// index reaches ncoeff (src/decompressor.cpp:20-27), as here.  `want`: the
-// ncoeff field the caller expects, W*H*D, or -L for a multi-level unit
-// (wc_inverse_levels): every other path rejects such a payload here.
-__device__ __forceinline__ bool read_header(const UnitDev& U, const uint8_t* __restrict__ ph, int32_t& nrle,
-                                            int32_t want) {
-    const int32_t* h = reinterpret_cast<const int32_t*>(ph);
-    nrle = h[4];
-    return h[0] == U.nx && h[1] == U.ny && h[2] == U.nz && h[3] == want && nrle >= 0;
-}
-__device__ __forceinline__ bool read_header(const UnitDev& U, const uint8_t* __restrict__ ph, int32_t& nrle) {
-    return read_header(U, ph, nrle, (int32_t)U.ncells);
-}
-
-// The same with saturating adds (v_add_u32 clamp): positions at or past
-// ncoeff (< 2^31) are all "dropped", so sums clamped at 2^32 - 1 decide the
-// same rows as exact ones.
-__device__ __forceinline__ uint32_t sat_add(uint32_t a, uint32_t b) { return __builtin_elementwise_add_sat(a, b); }
-
-__device__ __forceinline__ uint32_t wave_incl_sum32_sat(uint32_t v) {
-    v = sat_add(v, __builtin_amdgcn_update_dpp(0u, v, 0x111, 0xf, 0xf, false));
-    v = sat_add(v, __builtin_amdgcn_update_dpp(0u, v, 0x112, 0xf, 0xf, false));
-    v = sat_add(v, __builtin_amdgcn_update_dpp(0u, v, 0x114, 0xf, 0xf, false));
-    v = sat_add(v, __builtin_amdgcn_update_dpp(0u, v, 0x118, 0xf, 0xf, false));
-    v = sat_add(v, __builtin_amdgcn_update_dpp(0u, v, 0x142, 0xa, 0xf, false));
-    v = sat_add(v, __builtin_amdgcn_update_dpp(0u, v, 0x143, 0xc, 0xf, false));
-    return v;
-}
+constexpr int kDecChunk = 4096;  // floats per write round (16 KB of LDS)
 
 // Row index of the row-indexed units.  Only the runs are needed (the values
-// stay in the payload for K6r).  A negative run (malformed; the reference's
-// behaviour is undefined) counts as run 0, so positions never decrease and
-// every row entry is written: K6r never sees a stale or out-of-range entry.
-//
-// One block per pair tile of the plan (rdtiles: interleaved by tile index
-// across units, so a tile's look-back waits only on lower block ids, DESIGN.md
-// §Forward progress; or the tile index from a per-unit ticket); blocks past
-// the payload's pair tiles exit after the header.  The look-back granules are
-// epoch-tagged: no zeroing between calls.
+// stay in the payload for K6r).  Sums are Sat32: a negative run counts as run
+// 0, so positions never decrease and every row entry is written: K6r never
+// sees a stale or out-of-range entry.  One block per pair tile of the plan
+// (rdtiles).  The look-back granules are epoch-tagged: no zeroing between calls.
 
 #ifndef WC_RIX_MINB
 #define WC_RIX_MINB 8  // waves per SIMD the register budget is sized for (4-wave blocks: 8 per CU, <= 64 VGPRs)
@@ -104,80 +68,30 @@ __global__ __launch_bounds__(kThreads, WC_RIX_MINB) void k_rowindex(const UnitDe
     const UnitDev U = cst(units)[u];  // scalar copy: no reloads after the stores below
     const uint8_t* ph = payload + cst(offsets)[u];
     int32_t nrle;
-    const bool hok = read_header(U, ph, nrle);
+    const bool hok = header_ok(U.nx, U.ny, U.nz, (int32_t)U.ncells, ph, nrle);
     const uint32_t n = hok ? (uint32_t)nrle : 0u;
     if (ft.index == 0 && tid == 0) npairs[u] = n;  // K6r bounds its pair indices by it
     // tiles up to the one holding the virtual pair k = n (the plan launches
     // floor(ncoeff / kRixTile) + 1, enough for the first dropped pair)
-    if (ft.index > n / (uint32_t)kRixTile) return;  // uniform
-    uint32_t t = ordered == 2 ? n / (uint32_t)kRixTile - ft.index : ft.index;  // 2: reversed (test hook)
-    if (!ordered) {
-        if (tid == 0) s_x[0] = atomicAdd(ticket + u, 1u);
-        __syncthreads();
-        t = s_x[0];
-    }
+    const uint32_t ntile = n / (uint32_t)kRixTile + 1u;
+    if (ft.index >= ntile) return;  // uniform; before any atomic (wc_pairscan.h)
+    using Scan = PairScan<Sat32, GranuleEpoch32, kRixTile, LoadRuns>;
+    const uint32_t t = Scan::tile_index(ft.index, ntile, ordered, ticket + u, s_x);
     const uint32_t* __restrict__ runs = reinterpret_cast<const uint32_t*>(ph + 20);
+    const uint32_t kw = Scan::wave_first(t, w);
     uint32_t v[kRixRounds5];
-    {
-        const uint32_t kw = t * (uint32_t)kRixTile + (uint32_t)w * (kRixTile / 4);
 #pragma unroll
-        for (int r = 0; r < kRixRounds5; ++r) {
-            const uint32_t k = kw + r * 64 + l;
-            // nontemporal: K5 -12 % at C2, K6r after it +1 %, C5 even (profiles/r05/experiments/gpu_nt.txt)
-            v[r] = k < n ? __builtin_nontemporal_load(runs + 2 * k) : 0u;
-        }
-    }
+    for (int r = 0; r < kRixRounds5; ++r) v[r] = Scan::load(runs, kw + r * 64 + l, n);
     if (!hok && t == 0 && tid == 0) atomicOr(err, kErrHeader);
 
-    // 1. v = run + 1 (k < n), 0 (k >= n) -> saturating in-wave inclusive sums
-    const uint32_t kw = t * (uint32_t)kRixTile + (uint32_t)w * (kRixTile / 4);
-    bool neg = false;
-    uint32_t wsum = 0;
+    // 1. in-wave inclusive sums of run + 1; 2. the sum over the unit's earlier tiles
+    Scan::WaveSums ws;
 #pragma unroll
-    for (int r = 0; r < kRixRounds5; ++r) {
-        const uint32_t k = kw + r * 64 + l;
-        const int32_t run = (int32_t)v[r];
-        neg |= k < n && run < 0;
-        const uint32_t x = k < n ? (run < 0 ? 1u : (uint32_t)run + 1u) : 0u;
-        const uint32_t s = wave_incl_sum32_sat(x);
-        s_v[r][tid] = sat_add(wsum, s);
-        wsum = sat_add(wsum, __builtin_amdgcn_readlane(s, 63));
-    }
-    if (neg) atomicOr(err, kErrNegativeRun);
-    if (l == 0) s_w[w] = wsum;
-    __syncthreads();
-    uint32_t wexcl = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        wexcl = i < w ? sat_add(wexcl, s_w[i]) : wexcl;
-        tot = sat_add(tot, s_w[i]);
-    }
-
-    // 2. the sum over the unit's earlier tiles: look-back
-    if (w == 0) {
-        unsigned long long* st = status + U.dt_begin;
-        uint32_t excl = 0;
-        if (t == 0) {
-            if (l == 0) st_rlx(st, granule_e(kFlagIncl, epoch, tot));
-        } else {
-            if (l == 0) st_rlx(st + t, granule_e(kFlagAgg, epoch, tot));
-            // a predecessor tile unpublished after the wait bound: its sum from its pairs
-            excl = lookback_sum32e(st, (int64_t)t, l, err, epoch, [&](int64_t j) -> uint32_t {
-                const uint32_t k0 = (uint32_t)j * (uint32_t)kRixTile, k1 = min(k0 + (uint32_t)kRixTile, n);
-                uint32_t a = 0;
-                for (uint32_t k = k0 + (uint32_t)l; k < k1; k += 64) {
-                    const int32_t run = (int32_t)runs[2 * k];
-                    a = sat_add(a, run < 0 ? 1u : (uint32_t)run + 1u);
-                }
-                return __builtin_amdgcn_readlane(wave_incl_sum32_sat(a), 63);
-            });
-            if (l == 0) st_rlx(st + t, granule_e(kFlagIncl, epoch, sat_add(excl, tot)));
-        }
-        if (l == 0) s_x[1] = (uint32_t)excl;
-    }
-    __syncthreads();
+    for (int r = 0; r < kRixRounds5; ++r) s_v[r][tid] = ws.round(v[r], kw + r * 64 + l, n);
+    const Scan::Prefix P = Scan::prefix(ws.finish(err), t, n, runs, status + U.dt_begin, GranuleEpoch32{epoch & kEpochMask},
+                                        err, s_w, s_x, w, l);
     const uint32_t nc = (uint32_t)U.ncells;
-    const uint32_t A = sat_add(s_x[1], wexcl);
+    const uint32_t A = sat_add(P.excl, P.wexcl);
 
     // 3. row entries.  Pair k covers rows (rhi_{k-1}, rhi_k], rhi_k =
     // floor(ph_k / D) with ph_k = min(p_k, ncoeff) (p_k = S - 1, S the
@@ -218,100 +132,50 @@ __global__ __launch_bounds__(kThreads) void k_decode(const UnitDev* __restrict__
                                                    uint32_t* __restrict__ err, int ordered,
                                                    const int32_t* __restrict__ levels, uint32_t* __restrict__ bad) {
     __shared__ __attribute__((aligned(16))) float buf[kDecChunk];
-    __shared__ unsigned long long s_w[4];
-    __shared__ unsigned long long s_x[2];
+    using Scan = PairScan<Exact64, Granule62, kFlatTile, LoadPairs>;
+    __shared__ Scan::T s_w[4];
+    __shared__ Scan::V s_x[2];
     const int tid = threadIdx.x, l = tid & 63, w = tid >> 6;
     const FTile ft = tiles[blockIdx.x];
     const uint32_t u = ft.unit;
     const UnitDev& U = units[u];
     const uint8_t* ph = payload + offsets[u];
     int32_t nrle;
-    bool hok;
+    const int32_t want = LV && levels[u] >= 2 ? -levels[u] : (int32_t)U.ncells;
+    const bool hok = header_ok(U.nx, U.ny, U.nz, want, ph, nrle);
     if constexpr (LV) {
-        hok = read_header(U, ph, nrle, levels[u] >= 2 ? -levels[u] : (int32_t)U.ncells);
         if (ft.index == 0 && tid == 0) {
-            bad[u] = hok ? 0u : 1u;
+            bad[u] = hok ? kUnitRun : kUnitRefused;
             if (!hok) atomicOr(err, kErrHeader);
         }
         if (!hok) return;  // uniform
-    } else {
-        hok = read_header(U, ph, nrle);
     }
     const int64_t n = hok ? nrle : 0;
     const uint32_t ntile = n ? (uint32_t)((n + kFlatTile - 1) / kFlatTile) : 1u;
     // The plan launches ceil(ncoeff / kFlatTile) blocks per unit; those whose
-    // plan index is past the payload's pair tiles exit before any atomic.
+    // plan index is past the payload's pair tiles exit before any atomic
+    // (wc_pairscan.h).
     if (ft.index >= ntile) return;  // uniform
-    // Tile index: ordered form (WC_OPT_ORDERED 1) = plan index: the plan
-    // interleaves tiles by index across units, so a tile's look-back waits
-    // only on lower block ids of its unit (DESIGN.md §Forward progress);
-    // ticket form = the unit's next ticket, whatever the dispatch order.
-    uint32_t t = ordered == 2 ? ntile - 1u - ft.index : ft.index;  // 2: reversed (test hook)
-    if (!ordered) {
-        if (tid == 0) s_x[0] = atomicAdd(ticket + u, 1u);
-        __syncthreads();
-        t = (uint32_t)s_x[0];
-    }
+    const uint32_t t = Scan::tile_index(ft.index, ntile, ordered, ticket + u, s_x);
     if (!hok && t == 0 && tid == 0) atomicOr(err, kErrHeader);
 
-    // 1. this lane's pairs and their in-wave inclusive sums of (run + 1)
-    const uint2* __restrict__ pr = reinterpret_cast<const uint2*>(ph + 20);
-    const int64_t kw = (int64_t)t * kFlatTile + (int64_t)w * (kFlatTile / 4);
-    uint2 q[kDecRounds];
+    // 1. this lane's pairs and their in-wave inclusive sums of (run + 1);
+    // 2. start of this tile's range: the sum over the unit's earlier tiles
+    const uint32_t* __restrict__ runs = reinterpret_cast<const uint32_t*>(ph + 20);
+    const int64_t kw = Scan::wave_first(t, w);
+    uint2 q[Scan::kRounds];
 #pragma unroll
-    for (int r = 0; r < kDecRounds; ++r) {
-        const int64_t k = kw + r * 64 + l;
-        q[r] = k < n ? pr[k] : make_uint2(0u, 0u);
-    }
-    uint64_t incl[kDecRounds];
-    uint64_t wsum = 0;
-    bool neg = false;
+    for (int r = 0; r < Scan::kRounds; ++r) q[r] = Scan::load(runs, kw + r * 64 + l, n);
+    uint64_t incl[Scan::kRounds];
+    Scan::WaveSums ws;
 #pragma unroll
-    for (int r = 0; r < kDecRounds; ++r) {
-        const int64_t k = kw + r * 64 + l;
-        const int32_t run = (int32_t)q[r].x;
-        neg |= k < n && run < 0;
-        const uint64_t v = k < n ? (uint64_t)(int64_t)run + 1 : 0;
-        const uint64_t s = wave_incl_sum(v);
-        incl[r] = wsum + s;
-        wsum += ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(s >> 32), 63) << 32) |
-                __builtin_amdgcn_readlane((uint32_t)s, 63);
-    }
-    if (neg) atomicOr(err, kErrNegativeRun);
-    if (l == 0) s_w[w] = wsum;
-    __syncthreads();
-    uint64_t wexcl = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        wexcl += i < w ? s_w[i] : 0;
-        tot += s_w[i];
-    }
-
-    // 2. start of this tile's range: look-back over the unit's earlier tiles
-    if (w == 0) {
-        unsigned long long* st = status + U.dt_begin;
-        unsigned long long excl = 0;
-        if (t == 0) {
-            if (l == 0) st_rlx(st, kFlagIncl | (tot & kMask62));
-        } else {
-            if (l == 0) st_rlx(st + t, kFlagAgg | (tot & kMask62));
-            // a predecessor tile unpublished after the wait bound: its sum from its pairs
-            excl = lookback_sum62(st, (int64_t)t, l, err, [&](int64_t j) -> unsigned long long {
-                const int64_t k0 = j * kFlatTile, k1 = min(k0 + (int64_t)kFlatTile, n);
-                unsigned long long a = 0;
-                for (int64_t k = k0 + l; k < k1; k += 64) a += (unsigned long long)((int64_t)(int32_t)pr[k].x + 1);
-                return wave_sum(a);
-            });
-            if (l == 0) st_rlx(st + t, kFlagIncl | ((excl + tot) & kMask62));
-        }
-        if (l == 0) s_x[1] = excl;
-    }
-    __syncthreads();
+    for (int r = 0; r < Scan::kRounds; ++r) incl[r] = ws.round(q[r], kw + r * 64 + l, n);
+    const Scan::Prefix P = Scan::prefix(ws.finish(err), t, n, runs, status + U.dt_begin, Granule62{}, err, s_w, s_x, w, l);
     const uint64_t nc = U.ncells;
-    const uint64_t A = s_x[1];
+    const uint64_t A = P.excl;
     const uint64_t Ac = A < nc ? A : nc;
-    const uint64_t B = (t + 1 == ntile || tot >= nc - Ac) ? nc : Ac + tot;
-    const uint64_t base = A + wexcl - 1;  // + incl[r]: position of the lane's pair in round r
+    const uint64_t B = (t + 1 == ntile || P.tot >= nc - Ac) ? nc : Ac + P.tot;
+    const uint64_t base = A + P.wexcl - 1;  // + incl[r]: position of the lane's pair in round r
 
     // 3. write [Ac, B): zeros with this tile's pairs dropped in
     float* __restrict__ dst = flat + U.coef_off;
@@ -320,7 +184,7 @@ __global__ __launch_bounds__(kThreads) void k_decode(const UnitDev* __restrict__
         for (int i = tid; i < kDecChunk / 4; i += kThreads) b4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         __syncthreads();
 #pragma unroll
-        for (int r = 0; r < kDecRounds; ++r) {
+        for (int r = 0; r < Scan::kRounds; ++r) {
             const int64_t k = kw + r * 64 + l;
             const uint64_t o = base + incl[r] - c0;
             if (k < n && o < (uint64_t)kDecChunk) buf[o] = __uint_as_float(q[r].y);
@@ -345,6 +209,33 @@ __global__ __launch_bounds__(kThreads) void k_decode(const UnitDev* __restrict__
 
 
 // ---------------------------------------------------------------------------
+// Inverse of one 2x2x2 block (src/decompressor.cpp:89-156: X, then Y, then Z
+// pairs avg +/- diff): c[sz][sy][sx] -> V[dz][dy][dx].  K6 and K6r.
+__device__ __forceinline__ void synth_block(const float (&c)[2][2][2], float (&V)[2][2][2]) {
+    float X[2][2][2], Y[2][2][2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            X[s][t][0] = c[s][t][0] + c[s][t][1];
+            X[s][t][1] = c[s][t][0] - c[s][t][1];
+        }
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int x = 0; x < 2; ++x) {
+            Y[s][0][x] = X[s][0][x] + X[s][1][x];
+            Y[s][1][x] = X[s][0][x] - X[s][1][x];
+        }
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int x = 0; x < 2; ++x) {
+            V[0][t][x] = Y[0][t][x] + Y[1][t][x];
+            V[1][t][x] = Y[0][t][x] - Y[1][t][x];
+        }
+}
+
 // K6: inverse transform over the same 2x2x2-block tiles as K1.
 // Phase 1: flat rows (contiguous along K) -> LDS.  Phase 2: per block X, then Y,
 // then Z synthesis (src/decompressor.cpp:89-156); blocks with an odd tail on any
@@ -357,8 +248,8 @@ __global__ __launch_bounds__(kThreads) void k_inverse(const float* __restrict__ 
                                                     float* __restrict__ out, const uint32_t* __restrict__ bad) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const XTile td = tiles[blockIdx.x];
-    if constexpr (SKIP)  // wc_inverse_levels: a unit whose header disagreed stays untouched
-        if (bad[td.unit]) return;
+    if constexpr (SKIP)  // wc_inverse_levels, wc_inverse_coarse: only units marked kUnitRun are written
+        if (bad[td.unit] != kUnitRun) return;
     const UnitDev& U = units[td.unit];
     const int W = U.nx, H = U.ny, D = U.nz;
     const int hx = U.hx, hy = U.hy, hz = U.hz;
@@ -409,32 +300,7 @@ __global__ __launch_bounds__(kThreads) void k_inverse(const float* __restrict__ 
                         const int row = ((((t << lby) + byl) * 2 + x) << lbx) + bxl;
                         c[s][t][x] = lds[row * rstride + (s << lbz) + bzl];
                     }
-            // X first: X[sz][sy][dx]
-            float X[2][2][2];
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    X[s][t][0] = c[s][t][0] + c[s][t][1];
-                    X[s][t][1] = c[s][t][0] - c[s][t][1];
-                }
-            // then Y: Y[sz][dy][dx]
-            float Y[2][2][2];
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int x = 0; x < 2; ++x) {
-                    Y[s][0][x] = X[s][0][x] + X[s][1][x];
-                    Y[s][1][x] = X[s][0][x] - X[s][1][x];
-                }
-            // then Z
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int x = 0; x < 2; ++x) {
-                    V[0][t][x] = Y[0][t][x] + Y[1][t][x];
-                    V[1][t][x] = Y[0][t][x] - Y[1][t][x];
-                }
+            synth_block(c, V);
         } else {
 #pragma unroll
             for (int s = 0; s < 2; ++s)
@@ -474,7 +340,7 @@ __global__ __launch_bounds__(kThreads) void k_inverse_fast(const float* __restri
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const XTile td = tiles[blockIdx.x];
     if constexpr (SKIP)
-        if (bad[td.unit]) return;
+        if (bad[td.unit] != kUnitRun) return;
     const UnitDev& U = units[td.unit];
     const int W = U.nx, H = U.ny, D = U.nz;
     const int hx = U.hx, hy = U.hy, hz = U.hz;
@@ -517,7 +383,7 @@ __global__ __launch_bounds__(kThreads) void k_inverse_fast(const float* __restri
         const int bzq = ci >> (lbx + lby);
         const int bx = td.bx0 + bxl, by = td.by0 + byl, bzb = td.bz0 + 4 * bzq;
         if (bx >= hx || by >= hy || bzb >= hz) continue;
-        float c[2][2][2][4];  // [sz][sy][sx][z-block]
+        float c[4][2][2][2];  // [z-block][sz][sy][sx]
 #pragma unroll
         for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -526,35 +392,15 @@ __global__ __launch_bounds__(kThreads) void k_inverse_fast(const float* __restri
                 for (int x = 0; x < 2; ++x) {
                     const int row = ((((t << lby) + byl) * 2 + x) << lbx) + bxl;
                     const float4 v = *reinterpret_cast<const float4*>(lds + row * rstride + (s << lbz) + 4 * bzq);
-                    c[s][t][x][0] = v.x;
-                    c[s][t][x][1] = v.y;
-                    c[s][t][x][2] = v.z;
-                    c[s][t][x][3] = v.w;
+                    c[0][s][t][x] = v.x;
+                    c[1][s][t][x] = v.y;
+                    c[2][s][t][x] = v.z;
+                    c[3][s][t][x] = v.w;
                 }
 #pragma unroll
         for (int qb = 0; qb < 4; ++qb) {
-            float X[2][2][2], Y[2][2][2], V[2][2][2];
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    X[s][t][0] = c[s][t][0][qb] + c[s][t][1][qb];
-                    X[s][t][1] = c[s][t][0][qb] - c[s][t][1][qb];
-                }
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int x = 0; x < 2; ++x) {
-                    Y[s][0][x] = X[s][0][x] + X[s][1][x];
-                    Y[s][1][x] = X[s][0][x] - X[s][1][x];
-                }
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int x = 0; x < 2; ++x) {
-                    V[0][t][x] = Y[0][t][x] + Y[1][t][x];
-                    V[1][t][x] = Y[0][t][x] - Y[1][t][x];
-                }
+            float V[2][2][2];
+            synth_block(c[qb], V);
 #pragma unroll
             for (int dz = 0; dz < 2; ++dz)
 #pragma unroll
@@ -701,33 +547,6 @@ __device__ __forceinline__ void rix_scatter_range(float* __restrict__ reg, int R
         if (m != m0 || !have0) q = i < cnt ? pr[ks + i] : make_uint2(0u, 0u);
         carry = rix_round(rg, rlen, q, i, cnt, carry);
     }
-}
-
-// Inverse of one 2x2x2 block (src/decompressor.cpp:89-156: X, then Y, then Z
-// pairs avg +/- diff): c[sz][sy][sx] -> V[dz][dy][dx].
-__device__ __forceinline__ void synth_block(const float (&c)[2][2][2], float (&V)[2][2][2]) {
-    float X[2][2][2], Y[2][2][2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            X[s][t][0] = c[s][t][0] + c[s][t][1];
-            X[s][t][1] = c[s][t][0] - c[s][t][1];
-        }
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int x = 0; x < 2; ++x) {
-            Y[s][0][x] = X[s][0][x] + X[s][1][x];
-            Y[s][1][x] = X[s][0][x] - X[s][1][x];
-        }
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int x = 0; x < 2; ++x) {
-            V[0][t][x] = Y[0][t][x] + Y[1][t][x];
-            V[1][t][x] = Y[0][t][x] - Y[1][t][x];
-        }
 }
 
 // The prefetch of a tile's pairs into q: the first round of each range.
@@ -1129,7 +948,7 @@ static uint32_t resident_grid(const void* fn, size_t lds) {
 // The pair count of every unit's payload, checked against the unit (the row
 // index of wc_inverse_rows comes from the caller, so k_rowindex, which checks
 // the headers otherwise, does not run): npairs[u] = nrle, or 0 and kErrHeader
-// for a header that disagrees (read_header).
+// for a header that disagrees (header_ok).
 __global__ __launch_bounds__(kThreads) void k_pair_counts(const UnitDev* __restrict__ units, int n,
                                                         const uint8_t* __restrict__ payload,
                                                         const uint64_t* __restrict__ offsets,
@@ -1139,7 +958,7 @@ __global__ __launch_bounds__(kThreads) void k_pair_counts(const UnitDev* __restr
     const UnitDev& U = units[u];
     if (!U.rix) return;
     int32_t nrle;
-    const bool ok = read_header(U, payload + offsets[u], nrle);
+    const bool ok = header_ok(U.nx, U.ny, U.nz, (int32_t)U.ncells, payload + offsets[u], nrle);
     npairs[u] = ok ? (uint32_t)nrle : 0u;
     if (!ok) atomicOr(err, kErrHeader);
 }

@@ -123,7 +123,7 @@ __global__ __launch_bounds__(kThreads) void k_level(const UnitDev* __restrict__ 
                                                    float* __restrict__ side, unsigned long long* __restrict__ key,
                                                    const uint32_t* __restrict__ bad) {
     const uint2 it = items[blockIdx.x];
-    if (bad && bad[it.x]) return;  // inverse: the decode found the unit's header wrong and wrote nothing
+    if (bad && bad[it.x] != kUnitRun) return;  // inverse: the decode refused the unit or its corner is its result
     const UnitDev& U = units[it.x];
     const LvBox B = lv_box(U, shift, it.y);
     const float* __restrict__ A = coef + U.coef_off;
@@ -247,7 +247,7 @@ __global__ __launch_bounds__(kThreads) void k_level_copy(const UnitDev* __restri
                                                        const float* __restrict__ side, float* __restrict__ coef,
                                                        const uint32_t* __restrict__ bad) {
     const uint2 it = items[blockIdx.x];
-    if (bad && bad[it.x]) return;
+    if (bad && bad[it.x] != kUnitRun) return;
     const UnitDev& U = units[it.x];
     const LvBox B = lv_box(U, shift, it.y);
     const float* __restrict__ T = side + (U.coef_off >> 3);
