@@ -130,7 +130,11 @@ int wc_synchronize(wc_ctx* ctx);  /* also reports (and clears) kernel-side error
  *   coefficient scratch first (4 B/cell written and read back).  Same cells.
  * WC_OPT_RIX_LDS (default 9216), WC_OPT_RIX_TX (default 4): tile shape of the
  *   row-indexed inverse: LDS floats per workgroup (1024..16384) and log2 of the
- *   tile's blocks along x (0..5); y takes the rest of the budget.  Same cells.
+ *   tile's blocks along x (0..5); y takes the rest of the budget.  A unit
+ *   whose one-block tile needs more than the budget, 4 * D + 80 floats (D > 236
+ *   at 1024, D > 2284 at the default), decodes densely, as with
+ *   WC_OPT_INVERSE_ROWS 0.  The largest budget is a 64 KB tile, which
+ *   launches as it is.  Same cells.
  * WC_OPT_RIX_BLOCKED (default 0): each workgroup of the row-indexed inverse
  *   runs a contiguous run of tiles (0: tiles b, b + grid, ...).  Same cells.
  * WC_OPT_HOST_CHUNK (default 2^25 cells): wc_forward_host splits a batch of

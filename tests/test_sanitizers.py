@@ -9,7 +9,9 @@ CLI's argument errors, and the core library's host pool + destination
 prefault of the _host entry points (csrc/wc_hostmem.cpp, tests/cpp/
 test_hostmem.cpp), and the _host entry points' pipeline itself (csrc/
 wc_hostpipe.cpp + wc_common.cpp) over a CPU fake of the HIP runtime with
-injected failures (tests/cpp/test_hostpipe.cpp).  Any sanitizer report fails
+injected failures (tests/cpp/test_hostpipe.cpp), and the plan builder
+(csrc/wc_plan.cpp) under every tiling option of the row-indexed inverse over
+the same fake (tests/cpp/test_plan.cpp).  Any sanitizer report fails
 the test (halt_on_error)."""
 import lzma
 import os
@@ -107,4 +109,22 @@ def test_host_pipeline_under_sanitizer(san_bins, san, tmp_path):
     r = subprocess.run([str(san_bins[san] / "test_hostpipe")], capture_output=True, text=True, timeout=600,
                        env=san_env(tmp_path))
     check_clean(r, f"{san} test_hostpipe")
+    assert r.returncode == 0 and " 0 failed" in r.stdout, r.stdout + r.stderr
+
+
+@pytest.mark.parametrize("san", SANS)
+def test_plan_builder_under_sanitizer(san_bins, san, tmp_path):
+    """get_plan / ensure_scratch (csrc/wc_plan.cpp) over the fake runtime, for the
+    batch of tests/test_gpu_rix_options.py under WC_OPT_RIX_LDS {1024, 2048, 9216,
+    16384} x WC_OPT_RIX_TX 0..5 x WC_OPT_RIX_XCD x WC_OPT_INV_GROUPS {1, 3}: the
+    K6r tiles partition every row-indexed unit, fit the budget and the 64 KB
+    launch limit, fall back to the dense decode exactly past 4 D + 80 floats;
+    the kernel's LDS, row-index and cell addresses (restated from
+    wc_inverse.hip) stay in range and write every cell once; nat, the XCD
+    permutation, the group boundaries and the row-index tile order are
+    consistent; the scratch is large enough; a plan evicted from the cache is
+    rebuilt the same (tests/cpp/test_plan.cpp)."""
+    r = subprocess.run([str(san_bins[san] / "test_plan")], capture_output=True, text=True, timeout=600,
+                       env=san_env(tmp_path))
+    check_clean(r, f"{san} test_plan")
     assert r.returncode == 0 and " 0 failed" in r.stdout, r.stdout + r.stderr
