@@ -33,6 +33,19 @@
 //   cache      more than 16 distinct plans of the same units, then the first
 //              option set again: the same tile list as the first time.
 // Failure messages name the option set and the unit.
+//
+// A third batch: the units with one long axis of tests/long_axis_shapes.py (kLong
+// below: same dims, same cell offsets, and the class table of that file).  Its
+// fast-shape units of at most 300 000 cells go through the same checks at
+// WC_OPT_RIX_LDS {9216, 16384} (and 9200, where 4 D + 80 equals the budget for D =
+// 2280) x WC_OPT_RIX_TX {0, 4, 5}; the fallback boundaries 2280 / 2288 and 4072 /
+// 4080 and every unit's K6r tile shape are compared with the table.  The whole
+// list, the 2^21-cell units included, is planned once for the forward's fields:
+//   forward    fast, sparse, lbx / lby / lbz, ntx, net, et_begin, the emit class
+//              (which launch a unit's emit blocks are in, each tile once, in
+//              order) and the emit descriptor's copies of the unit fields;
+//   dmagic     div_rows (wc_device.h) restated: floor(p / D) at p = q D - 1, q D
+//              and q D + 1 for every row q of the unit, and at 2^31 - 1.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -608,10 +621,257 @@ static size_t sweep_batch(bool fast_only, Seen& seen) {
     return plans;
 }
 
+// The units of tests/long_axis_shapes.py (UNITS + RIX16K, in that order, at layout()'s cell
+// offsets) with its class table CLASSES; tests/test_long_axis_cpu.py compares these rows with
+// that file.  rix: {ilbx, ilby} at that WC_OPT_RIX_LDS and WC_OPT_RIX_TX 4, {-1, -1}: dense decode.
+struct LongUnit {
+    const char* tag;
+    int w, h, d;
+    uint64_t off;
+    int fast, sparse, lbx, lby, lbz, big;
+    uint32_t net, ntx;
+    int rix9216[2], rix16384[2];
+};
+static const LongUnit kLong[] = {
+    {"big_x", 2048, 32, 32, 3, 1, 1, 5, 1, 4, 1, 128, 256, {4, 2}, {4, 2}},
+    {"big_y", 32, 2048, 32, 2097157, 1, 1, 4, 2, 4, 1, 128, 256, {4, 2}, {4, 2}},
+    {"big_z", 32, 32, 2048, 4194316, 1, 1, 4, 1, 5, 1, 128, 256, {0, 0}, {0, 0}},
+    {"below_big", 2046, 32, 32, 6291471, 1, 1, 5, 1, 4, 0, 256, 256, {4, 2}, {4, 2}},
+    {"s32_x", 2048, 2, 64, 8386584, 1, 1, 5, 0, 5, 0, 32, 32, {4, 0}, {4, 0}},
+    {"s32_z", 64, 2, 2048, 8648736, 1, 1, 5, 0, 5, 0, 32, 32, {0, 0}, {0, 0}},
+    {"pencil_x", 4096, 2, 8, 8910887, 1, 0, 5, 0, 2, 0, 8, 64, {4, 0}, {4, 0}},
+    {"s32_y", 64, 34, 64, 8976428, 1, 1, 5, 0, 5, 0, 17, 17, {4, 1}, {4, 1}},
+    {"pencil_y", 2, 4096, 8, 9115692, 1, 0, 0, 8, 2, 0, 8, 8, {0, 8}, {0, 8}},
+    {"pencil_z", 2, 2, 4096, 9181235, 1, 1, 0, 0, 5, 0, 2, 64, {-1, -1}, {-1, -1}},
+    {"rix_edge_in", 2, 2, 2280, 9197626, 1, 0, 0, 0, 5, 0, 2, 36, {0, 0}, {0, 0}},
+    {"rix_edge_out", 2, 2, 2288, 9206751, 1, 0, 0, 0, 5, 0, 2, 36, {-1, -1}, {0, 0}},
+    {"rix_edge_wide", 4, 6, 2280, 9215905, 1, 0, 1, 2, 5, 0, 7, 36, {0, 0}, {0, 0}},
+    {"magic_d_x", 130, 2, 1000, 9270625, 1, 0, 5, 0, 5, 0, 32, 48, {1, 0}, {2, 0}},
+    {"magic_d_y", 2, 130, 1000, 9530633, 1, 0, 0, 5, 5, 0, 32, 48, {0, 1}, {0, 2}},
+    {"magic_d_3000", 8, 8, 3000, 9790635, 1, 0, 2, 2, 5, 0, 24, 47, {-1, -1}, {0, 0}},
+    {"magic_d_200", 66, 2, 200, 9982641, 1, 0, 5, 0, 5, 0, 4, 8, {3, 0}, {4, 0}},
+    {"lx_shrink_264", 256, 2, 264, 10009045, 1, 0, 5, 0, 5, 0, 17, 20, {3, 0}, {3, 0}},
+    {"lx_shrink_hx513", 1026, 4, 40, 10144217, 1, 0, 5, 0, 5, 0, 21, 34, {4, 1}, {4, 1}},
+    {"lx_shrink_hy513", 4, 1026, 24, 10308381, 1, 0, 1, 5, 4, 0, 13, 17, {1, 5}, {1, 6}},
+    {"lx_shrink_160", 192, 6, 160, 10406877, 1, 0, 5, 0, 5, 0, 23, 27, {3, 0}, {4, 0}},
+    {"slab_x", 320, 64, 8, 10591199, 1, 0, 5, 3, 2, 0, 20, 20, {4, 4}, {4, 4}},
+    {"slab_y", 64, 320, 8, 10755040, 1, 0, 5, 3, 2, 0, 20, 20, {4, 4}, {4, 4}},
+    {"odd_x", 2049, 3, 5, 10918881, 0, 0, 5, 1, 2, 0, 4, 33, {-1, -1}, {-1, -1}},
+    {"odd_y", 3, 2049, 5, 10949619, 0, 0, 1, 7, 2, 0, 4, 9, {-1, -1}, {-1, -1}},
+    {"odd_z", 3, 5, 2049, 10980358, 0, 0, 1, 2, 5, 0, 4, 33, {-1, -1}, {-1, -1}},
+    {"line_x", 4097, 1, 1, 11011097, 0, 0, 5, 0, 0, 0, 1, 65, {-1, -1}, {-1, -1}},
+    {"line_y", 1, 4097, 1, 11015195, 0, 0, 0, 10, 0, 0, 1, 3, {-1, -1}, {-1, -1}},
+    {"line_z", 1, 1, 4097, 11019299, 0, 0, 0, 0, 5, 0, 1, 65, {-1, -1}, {-1, -1}},
+    {"empty", 0, 2048, 8, 11023399, 0, 0, 0, 8, 2, 0, 1, 0, {-1, -1}, {-1, -1}},
+    {"s32_x_odd", 2048, 2, 64, 11023407, 1, 1, 5, 0, 5, 0, 32, 32, {4, 0}, {4, 0}},
+    {"s32_z_odd", 64, 2, 2048, 11285559, 1, 1, 5, 0, 5, 0, 32, 32, {0, 0}, {0, 0}},
+    {"s32_y_odd", 64, 34, 64, 11547705, 1, 1, 5, 0, 5, 0, 17, 17, {4, 1}, {4, 1}},
+    {"rix16k_in", 2, 2, 4072, 11686977, 1, 0, 0, 0, 5, 0, 2, 64, {-1, -1}, {0, 0}},
+    {"rix16k_out", 2, 2, 4080, 11703269, 1, 0, 0, 0, 5, 0, 2, 64, {-1, -1}, {-1, -1}},
+};
+static constexpr int kLongUnits = (int)(sizeof(kLong) / sizeof(kLong[0]));
+static constexpr uint64_t kLongPlanCells = 300000;  // long_axis_shapes.PLAN_CELLS
+
+// div_rows of wc_device.h, restated
+static uint32_t div_rows_host(uint32_t p, uint64_t dmagic) {
+    if ((uint32_t)dmagic == 0u) return p >> (uint32_t)(dmagic >> 32);
+    return (uint32_t)(((uint64_t)p * (uint32_t)dmagic) >> (uint32_t)(dmagic >> 32));
+}
+
+// The forward's fields of a plan of `rows` (a subset of kLong, in its order) against the table.
+static void check_forward_fields(const Plan& P, const std::vector<const LongUnit*>& rows, const char* t) {
+    const int n = (int)rows.size();
+    CHECK((int)P.units.size() == n, "%s: %zu unit descriptors", t, P.units.size());
+    if ((int)P.units.size() != n) return;
+    uint32_t et = 0, small_blocks = 0;
+    uint64_t row_entries = 0;
+    for (int i = 0; i < n; ++i) {
+        const UnitDev& d = P.units[i];
+        const LongUnit& L = *rows[i];
+        const char* g = L.tag;
+        CHECK(d.nx == L.w && d.ny == L.h && d.nz == L.d && d.cell_off == L.off, "%s, %s: dims %d x %d x %d at %llu", t, g, d.nx,
+              d.ny, d.nz, (unsigned long long)d.cell_off);
+        CHECK(d.fast == L.fast, "%s, %s: fast %d", t, g, d.fast);
+        CHECK((int)d.sparse == L.sparse, "%s, %s: sparse %u", t, g, d.sparse);
+        CHECK(d.lbx == L.lbx && d.lby == L.lby && d.lbz == L.lbz, "%s, %s: transform tile 2^(%d, %d, %d)", t, g, d.lbx, d.lby,
+              d.lbz);
+        CHECK(d.lbx + d.lby + d.lbz <= 10, "%s, %s: more than kMaxTileBlocks blocks per tile", t, g);
+        CHECK(d.ntx == L.ntx, "%s, %s: ntx %u", t, g, d.ntx);
+        CHECK(d.net == L.net, "%s, %s: net %u", t, g, d.net);
+        CHECK(d.et_begin == et, "%s, %s: et_begin %u after %u emit tiles", t, g, d.et_begin, et);
+        et += d.net;
+        CHECK((d.ncells >= kEmitBigCells) == (L.big != 0), "%s, %s: %llu cells, big %d", t, g, (unsigned long long)d.ncells, L.big);
+        if (!L.big) small_blocks += d.net;
+        CHECK(d.row_off == row_entries, "%s, %s: row_off %llu", t, g, (unsigned long long)d.row_off);
+        if (d.ncells) row_entries += (uint64_t)L.w * L.h + 1;
+        // the transform tiles of the unit: a grid of ntx tiles over its blocks, inside the unit
+        uint32_t tiles = 0;
+        for (const XTile& x : P.xtiles)
+            if (x.unit == (uint32_t)i) {
+                ++tiles;
+                CHECK((int)x.bx0 < d.nbx && (int)x.by0 < d.nby && (int)x.bz0 < d.nbz && x.bx0 % (1u << d.lbx) == 0 &&
+                          x.by0 % (1u << d.lby) == 0 && x.bz0 % (1u << d.lbz) == 0,
+                      "%s, %s: transform tile at block (%u, %u, %u)", t, g, x.bx0, x.by0, x.bz0);
+            }
+        CHECK(tiles == d.ntx, "%s, %s: %u transform tiles listed, ntx %u", t, g, tiles, d.ntx);
+        // dmagic: the shift form for D = 2^l, else m = floor(2^(31 + l) / D) + 1 with the shift 31 + l
+        if (!L.fast) {
+            CHECK(d.dmagic == 0, "%s, %s: dmagic %llx of a unit without a row index", t, g, (unsigned long long)d.dmagic);
+            continue;
+        }
+        const uint32_t D = (uint32_t)L.d;
+        const bool pow2 = (D & (D - 1)) == 0;
+        CHECK(((uint32_t)d.dmagic == 0u) == pow2, "%s, %s: dmagic %llx for D %u", t, g, (unsigned long long)d.dmagic, D);
+        CHECK((d.dmagic >> 32) == (uint64_t)ceil_log2(D) + (pow2 ? 0 : 31), "%s, %s: dmagic shift %llu", t, g,
+              (unsigned long long)(d.dmagic >> 32));
+        uint64_t bad = 0, first_bad = 0;
+        auto probe = [&](uint64_t p) {
+            if (p >= (uint64_t(1) << 31)) return;
+            ++g_checks;
+            if (div_rows_host((uint32_t)p, d.dmagic) != (uint32_t)(p / D) && !bad++) first_bad = p;
+        };
+        for (uint64_t q = 0; q <= (uint64_t)L.w * L.h; ++q) {
+            if (q) probe(q * D - 1);
+            probe(q * D);
+            probe(q * D + 1);
+        }
+        probe((uint64_t(1) << 31) - 1);
+        CHECK(bad == 0, "%s, %s: div_rows wrong at %llu positions, first p = %llu: %u, floor(p / %u) = %llu", t, g,
+              (unsigned long long)bad, (unsigned long long)first_bad, div_rows_host((uint32_t)first_bad, d.dmagic), D,
+              (unsigned long long)(first_bad / D));
+    }
+    CHECK(P.netiles == et, "%s: netiles %u of %u", t, P.netiles, et);
+    CHECK(P.rowinfo_entries == row_entries, "%s: %llu row entries", t, (unsigned long long)P.rowinfo_entries);
+    // emit blocks: [small-unit launch | big-unit launch], each tile of each unit once, a unit's tiles in order
+    CHECK(P.nedesc_small == small_blocks && P.edesc.size() == et, "%s: %u small emit blocks of %zu, expected %u of %u", t,
+          P.nedesc_small, P.edesc.size(), small_blocks, et);
+    std::vector<uint32_t> next(n, 0);
+    for (size_t k = 0; k < P.edesc.size(); ++k) {
+        const EmitDesc& e = P.edesc[k];
+        CHECK(e.unit < (uint32_t)n, "%s: emit block %zu of unit %u", t, k, e.unit);
+        if (e.unit >= (uint32_t)n) continue;
+        const UnitDev& d = P.units[e.unit];
+        const LongUnit& L = *rows[e.unit];
+        CHECK((k >= P.nedesc_small) == (L.big != 0), "%s, %s: emit block %zu in the %s launch", t, L.tag, k,
+              k >= P.nedesc_small ? "big" : "small");
+        CHECK(e.index == next[e.unit], "%s, %s: emit tile %u before tile %u", t, L.tag, e.index, next[e.unit]);
+        next[e.unit] = e.index + 1;
+        CHECK(e.coef_off == d.coef_off && e.pay_off == d.pay_off && e.ncells == d.ncells && e.et_begin == d.et_begin &&
+                  e.net == d.net && e.nx == d.nx && e.ny == d.ny && e.nz == d.nz,
+              "%s, %s: emit block %zu does not carry its unit's fields", t, L.tag, k);
+        CHECK((e.mode & 1u) == d.sparse && ((e.mode >> 1) & 7u) == (uint32_t)d.lbz && (e.mode >> 8) == (uint32_t)(d.dmagic >> 32) &&
+                  e.dmul == (uint32_t)d.dmagic,
+              "%s, %s: emit block %zu mode %x dmul %x", t, L.tag, k, e.mode, e.dmul);
+        CHECK(e.row_off == d.row_off && e.flag_off == (uint32_t)d.flag_off, "%s, %s: emit block %zu row_off %u flag_off %u", t, L.tag,
+              k, e.row_off, e.flag_off);
+    }
+    for (int i = 0; i < n; ++i) CHECK(next[i] == P.units[i].net, "%s, %s: %u of %u emit tiles listed", t, rows[i]->tag, next[i], P.units[i].net);
+}
+
+static int long_index(const std::vector<const LongUnit*>& rows, const char* tag) {
+    for (size_t i = 0; i < rows.size(); ++i)
+        if (std::strcmp(rows[i]->tag, tag) == 0) return (int)i;
+    CHECK(false, "long-axis batch: no unit %s", tag);
+    return 0;
+}
+
+// The third batch.
+static size_t sweep_long_axis(Seen& seen) {
+    g_batch = "long-axis batch";
+    size_t plans = 0;
+    // the fast-shape units of at most kLongPlanCells cells: every check of the other batches
+    std::vector<const LongUnit*> rows;
+    std::vector<wc_unit> units;
+    for (const LongUnit& L : kLong)
+        if (L.fast && (uint64_t)L.w * L.h * L.d <= kLongPlanCells) {
+            rows.push_back(&L);
+            units.push_back(wc_unit{L.off, L.w, L.h, L.d, 0});
+        }
+    CHECK(rows.size() == 24, "long-axis batch: %zu fast units of at most %llu cells", rows.size(), (unsigned long long)kLongPlanCells);
+    const int in9216 = long_index(rows, "rix_edge_in"), out9216 = long_index(rows, "rix_edge_out");
+    const int in16k = long_index(rows, "rix16k_in"), out16k = long_index(rows, "rix16k_out");
+    CHECK(rows[in9216]->d == 2280 && rows[out9216]->d == 2288 && rows[in16k]->d == 4072 && rows[out16k]->d == 4080,
+          "long-axis batch: the boundary units are not D = 2280 / 2288 / 4072 / 4080");
+    wc_ctx* c = make_ctx();
+    std::vector<Opt> sweep;
+    for (int lds : {9216, 16384})
+        for (int tx : {0, 4, 5}) {
+            sweep.push_back(Opt{lds, tx, 0, 1});
+            if (tx == 4) {
+                sweep.push_back(Opt{lds, tx, 0, 3});
+                sweep.push_back(Opt{lds, tx, 1, 1});
+            }
+        }
+    sweep.push_back(Opt{9200, 4, 0, 1});  // 4 D + 80 == the budget for D = 2280: still row-indexed
+    for (const Opt& o : sweep) {
+        if (build(c, units, o) != WC_OK) continue;
+        ++plans;
+        check_plan(c, units, o, seen);
+        const Plan& P = c->plan;
+        const std::string tag = o.str();
+        const char* t = tag.c_str();
+        check_forward_fields(P, rows, t);
+        // the fallback boundary of each budget, by name
+        const bool r2280 = P.units[in9216].rix, r2288 = P.units[out9216].rix, r4072 = P.units[in16k].rix, r4080 = P.units[out16k].rix;
+        if (o.lds == 9216 || o.lds == 9200)
+            CHECK(r2280 && !r2288 && !r4072 && !r4080, "%s: rix of 2 x 2 x 2280 / 2288 / 4072 / 4080 = %d / %d / %d / %d", t, r2280,
+                  r2288, r4072, r4080);
+        else
+            CHECK(r2280 && r2288 && r4072 && !r4080, "%s: rix of 2 x 2 x 2280 / 2288 / 4072 / 4080 = %d / %d / %d / %d", t, r2280, r2288,
+                  r4072, r4080);
+        for (size_t i = 0; i < rows.size(); ++i) {
+            const UnitDev& d = P.units[i];
+            const int* want = o.lds == 16384 ? rows[i]->rix16384 : rows[i]->rix9216;
+            if (want[0] < 0) {
+                CHECK(!d.rix, "%s, %s: row-indexed, the table says dense", t, rows[i]->tag);
+                // a dense fast unit: every transform tile once in the dense inverse list, one decode tile per 4096 cells
+                uint32_t ix = 0;
+                for (const XTile& x : P.ixtiles) ix += x.unit == (uint32_t)i;
+                CHECK(ix == d.ntx && d.nrt == 0, "%s, %s: %u dense inverse tiles of %u, %u K6r tiles", t, rows[i]->tag, ix, d.ntx, d.nrt);
+            } else if (o.tx == 4 && o.lds != 9200) {
+                CHECK(shape_is(P, (int)i, 1 << want[0], 1 << want[1]), "%s, %s: K6r tile 2^%d x 2^%d, the table says 2^%d x 2^%d", t,
+                      rows[i]->tag, d.ilbx, d.ilby, want[0], want[1]);
+            } else {
+                CHECK(d.rix && d.ilbx <= o.tx, "%s, %s: rix %d, K6r tile 2^%d x 2^%d", t, rows[i]->tag, d.rix, d.ilbx, d.ilby);
+            }
+        }
+    }
+    destroy_ctx(c);
+    // the whole list once, at the defaults: the forward's fields, the 2^21-cell units and the generic ones included
+    {
+        std::vector<const LongUnit*> all;
+        std::vector<wc_unit> all_units;
+        uint64_t end = 0;
+        for (const LongUnit& L : kLong) {
+            CHECK(L.off >= end && L.off <= end + 10, "long-axis batch, %s: offset %llu after %llu", L.tag, (unsigned long long)L.off,
+                  (unsigned long long)end);
+            end = L.off + (uint64_t)L.w * L.h * L.d;
+            all.push_back(&L);
+            all_units.push_back(wc_unit{L.off, L.w, L.h, L.d, 0});
+        }
+        wc_ctx* c2 = make_ctx();
+        const Opt o{9216, 4, 0, 1};
+        if (build(c2, all_units, o) == WC_OK) {
+            ++plans;
+            const std::string tag = o.str() + " (whole list)";
+            check_forward_fields(c2->plan, all, tag.c_str());
+            for (int i = 0; i < kLongUnits; ++i) {
+                const UnitDev& d = c2->plan.units[i];
+                const int* want = kLong[i].rix9216;
+                CHECK(want[0] < 0 ? !d.rix : shape_is(c2->plan, i, 1 << want[0], 1 << want[1]), "%s, %s: rix %d, K6r tile 2^%d x 2^%d",
+                      tag.c_str(), kLong[i].tag, d.rix, d.ilbx, d.ilby);
+            }
+        }
+        destroy_ctx(c2);
+    }
+    return plans;
+}
+
 int main() {
     Seen seen;
     size_t plans = sweep_batch(false, seen);
     plans += sweep_batch(true, seen);
+    plans += sweep_long_axis(seen);
     // every branch the device test is after was in the sweep
     CHECK(seen.tx32 && seen.ty32 && seen.tx1_aligned && seen.edge_x && seen.edge_y && seen.quad && seen.quad_edge &&
               seen.pair8 && seen.scalar && seen.fallback && seen.lds_63744,

@@ -57,9 +57,11 @@ def _dims(rng, n):
     return out
 
 
-def _field(rng, O, i, dims):
+def _field(rng, O, i, dims, kind=None):
+    """kind: 0..7 to pin the field (tests/long_axis_shapes.py); None draws it."""
     W, H, D = dims
-    kind = rng.integers(0, 8)
+    if kind is None:
+        kind = rng.integers(0, 8)
     if kind <= 2:  # the SURVEY §8(d) field
         return O.synth_box_f64(O.unit_seed(99, 1, i, int(kind)), (W * i % 997, 7 * i, 3 * i), W, H, D)
     if kind == 3:  # wide-range Gaussian, mixed sign
