@@ -341,9 +341,9 @@ int wc_forward_tol_host(wc_ctx* ctx, const void* cells, int dtype, const wc_unit
  * instead of decoding garbage, and a payload or .xz file describes itself.
  * Slot offsets, pair layout and wc_payload_bound do not change.
  *
- * The RMSE-tolerance mode is one-level only: with L >= 2 the basis vectors of
- * level l have squared norm 8^l, so its rule would need per-level weights.
- * There is no _tol form of these calls.
+ * wc_forward_tol is one-level only: with L >= 2 the basis vectors of level l
+ * have squared norm 8^l, so the rule needs per-level weights.  The _tol form of
+ * these calls is wc_forward_levels_tol below, with one threshold per level.
  *
  *   wc_levels_for: host-only; the largest L <= min(want, WC_MAX_LEVELS) with
  *     2^L dividing nx, ny and nz; 1 if none does or the box has no cells.
@@ -388,6 +388,84 @@ int wc_forward_levels_host(wc_ctx* ctx, const void* cells, int dtype, const wc_u
                            uint64_t payload_capacity, uint64_t* offsets, uint32_t* kept);
 int wc_inverse_levels_host(wc_ctx* ctx, const uint8_t* payload, const uint64_t* offsets, const wc_unit* units, int n,
                            const int32_t* levels, float* out);
+
+/* Opt-in RMSE tolerance on the multi-level transform (NOT the reference's
+ * rule): the tolerated RMSE of each unit, as wc_forward_tol, on the final array
+ * of wc_forward_levels, with one threshold per level.
+ *
+ * Setting.  A unit W x H x D with cells and L levels, 1 <= L <= WC_MAX_LEVELS;
+ * 2^L divides W, H and D (for L = 1: even dimensions, as wc_forward_tol
+ * demands).  A is the final flat array of wc_forward_levels in the x-slowest
+ * order (I*H + J)*D + K, N = W*H*D.
+ *
+ * Level of a coefficient.  j* is the largest j in 0..L-1 with I < W>>j,
+ * J < H>>j and K < D>>j; lvl(I, J, K) = j* + 1 (the low-pass corner has level
+ * L).  The basis vectors of level l have squared norm 8^l: dropping the set S
+ * costs SSE = sum_S 8^lvl * c^2, exact for the real-number transform;
+ * RMSE^2 = SSE / N.
+ *
+ * The selection rule, on the unit's tolerance tol (a double >= 0, +inf
+ * allowed; NaN or negative: WC_ERR_INVALID):
+ *   cnt[l][b] = coefficients of level l with fp32 bits of |c| >> WC_HIST_SHIFT
+ *               == b (the WC_HIST_BINS bins; NaN not counted)
+ *   hi_b      = as in wc_tol_threshold
+ *   budget    = (tol * tol) * (double)N
+ *   S = 0; visit the pairs (s, l) in lexicographic order, s = 0 .. 4095 +
+ *   WC_LTOL_SHIFT*(L-1), then l = 1..L, with b = s - WC_LTOL_SHIFT*(l-1)
+ *   (WC_LTOL_SHIFT = 24 bins = 1.5 octaves of 16 bins, about the factor sqrt(8)
+ *   between the levels' weights); a pair whose b is outside 0..4095 or whose
+ *   cnt[l][b] == 0 is skipped; at each visited pair
+ *       t = S + (double)cnt[l][b] * ((double)8^l * (hi_b * hi_b));
+ *       if !(t <= budget) stop at (s*, l*);  else S = t
+ *   bstar_l   = clamp(s* + (l < l* ? 1 : 0) - WC_LTOL_SHIFT*(l-1), 0, 4096), the
+ *               first kept bin of level l (no stop: 4096 for every level)
+ *   thresh_l  = from bstar_l as wc_tol_threshold's thresh from b*: 0.0f at 0,
+ *               FLT_MAX from 0xFF0 up, else the float with bits
+ *               (bstar_l << 19) - 1
+ *   bound     = sqrt(S / N) (0 when N == 0), bound <= tol
+ * in IEEE double, every multiply and add rounded on its own; 8^l is an exact
+ * double.  Only integer counts enter: the host, the device and every run give
+ * the same bits.  With L = 1 the rule is wc_tol_threshold operation for
+ * operation, and an L = 1 unit gets the bits and bytes of wc_forward_tol.
+ *
+ * Payload.  The pairs of exactly the coefficients with |c| > thresh_lvl
+ * (strict: NaN is never kept), in flat order, with the reference's run-length
+ * rule and serialisation and the header of wc_forward_levels (ncoeff = -L for
+ * L >= 2).  The format does not change: wc_inverse_levels, wc_inverse_coarse
+ * and their _host forms decode these payloads as they are.
+ *
+ *   wc_tol_levels_threshold: host-only; the rule on one unit's counts
+ *     (levels x WC_HIST_BINS uint64, level-major); thresh receives `levels`
+ *     floats, bound is nullable.  WC_ERR_INVALID for null pointers, a NaN or
+ *     negative tol, or levels outside 1..WC_MAX_LEVELS.
+ *   wc_forward_levels_tol: wc_forward_levels with per-unit tolerances in place
+ *     of keep / thresh.  levels (n int32) and tol (n doubles): HOST, consumed
+ *     before the call returns.  d_thresh: n x WC_MAX_LEVELS floats on the
+ *     device, nullable; unit u's level l at u*WC_MAX_LEVELS + l - 1, entries
+ *     past levels[u] written 0.0f.  d_bound: n doubles on the device, nullable.
+ *     Slots, offsets and wc_payload_bound as in wc_forward_levels.  The
+ *     coefficients are staged densely, read once for the bins and masked in
+ *     place by the per-level thresholds before the emit.  It leaves nothing
+ *     staged (there is no _emit form).  A unit without cells keeps nothing.
+ *   wc_forward_levels_tol_host: host buffers; payloads packed as
+ *     wc_forward_host; thresh (n x WC_MAX_LEVELS), bound, rmse (n each): host,
+ *     nullable; rmse = the ACTUAL RMSE of each unit's round trip, taken on the
+ *     device (wc_inverse_levels + wc_rmse).  The unit runs (WC_OPT_HOST_CHUNK)
+ *     go one after another.
+ * What wc_forward_levels refuses (a level outside 1..WC_MAX_LEVELS, a dimension
+ * that 2^L does not divide) and what wc_forward_tol refuses (a NaN or negative
+ * tolerance, a unit with cells and an odd dimension, which here can only be an
+ * L = 1 unit): WC_ERR_INVALID naming the unit, before anything is launched;
+ * outputs stay untouched. */
+#define WC_LTOL_SHIFT 24
+int wc_tol_levels_threshold(const uint64_t* counts, int levels, uint64_t ncoeff, double tol, float* thresh,
+                            double* bound);
+int wc_forward_levels_tol(wc_ctx* ctx, const void* d_cells, int dtype, const wc_unit* units, int n,
+                          const int32_t* levels, const double* tol, uint8_t* d_payload, uint64_t payload_capacity,
+                          uint64_t* d_offsets, uint32_t* d_kept, float* d_thresh, double* d_bound);
+int wc_forward_levels_tol_host(wc_ctx* ctx, const void* cells, int dtype, const wc_unit* units, int n,
+                               const int32_t* levels, const double* tol, uint8_t* payload, uint64_t payload_capacity,
+                               uint64_t* offsets, uint32_t* kept, float* thresh, double* bound, double* rmse);
 
 /* Opt-in reduced-resolution decode (not in the reference): the box at 1/2^r
  * resolution straight from a payload, without the work of the full resolution.
@@ -542,7 +620,8 @@ int wc_decompose_host(wc_ctx* ctx, const void* cells, int dtype, const wc_unit* 
 #define WC_STAGE_HIST 5       /* histogram pass of generic units (wc_forward_stage with d_hist; the fast
                                  units' bins are counted inside the transform stage) */
 #define WC_STAGE_PAIRS 6      /* header check + pair counts of wc_inverse_rows with a caller row index */
-#define WC_STAGE_TOL 7        /* per-unit bins + threshold pick of the RMSE-tolerance mode (wc_forward_tol) */
+#define WC_STAGE_TOL 7        /* per-unit bins + threshold pick of the RMSE-tolerance mode (wc_forward_tol); per-level bins, pick
+                                 and mask pass of wc_forward_levels_tol */
 #define WC_STAGE_LEVELS 8    /* level passes, key pass and header patch of the multi-level mode (wc_forward_levels,
                                  wc_inverse_levels) */
 #define WC_NUM_STAGES 9

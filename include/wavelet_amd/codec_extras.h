@@ -36,4 +36,15 @@ std::string xz_decompress(const std::string& xz);
 // other read errors do.
 Box3D decompress_coarse(const std::string& file_path, int reduce);
 
+// compress() with a tolerated RMSE in place of keep (GPU, wc_forward_levels_tol_host;
+// not in the reference): every component of the box is transformed with the levels
+// its dimensions admit, at most `levels` (wc_levels_for), and keeps what the
+// per-level thresholds of the tolerance leave, so that its round-trip RMSE stays
+// within `rmse` up to fp32 rounding.  Writes the usual per-box .xz files, which
+// decompress() and decompress_coarse() read as they are, and returns the structs.
+// A component with cells and an odd dimension has no such bound: the call exits
+// with the library's message, as the other errors do.
+std::vector<CompressedWavelet> compress_rmse(multiBox3D& box, std::vector<int> components, int levels, double rmse,
+                                             int time, int level, int box_index, std::string compressed_dir);
+
 }  // namespace wavelet_amd

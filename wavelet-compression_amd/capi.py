@@ -34,8 +34,10 @@ EXPORTED = (
     "wc_levels_for", "wc_payload_levels", "wc_forward_levels", "wc_decompose_levels",
     "wc_inverse_flat_levels", "wc_inverse_levels", "wc_forward_levels_host", "wc_inverse_levels_host",
     "wc_coarse_units", "wc_inverse_coarse", "wc_inverse_coarse_host",
+    "wc_tol_levels_threshold", "wc_forward_levels_tol", "wc_forward_levels_tol_host",
 )
 WC_MAX_LEVELS = 4  # levels of the opt-in multi-level transform (1 = the reference's codec)
+WC_LTOL_SHIFT = 24  # bins between the walks of two adjacent levels in the multi-level RMSE-tolerance rule
 WC_OPT_SPARSE = 12   # sparse coefficient staging in the forward (default 1)
 WC_OPT_ORDERED = 13  # look-back tile index from the launch order (1, default) or per-unit tickets (0)
 WC_OPT_INVERSE_ROWS = 14  # row-indexed inverse of even-dims units (1, default) or dense decode (0)
@@ -137,6 +139,10 @@ def load_library() -> ctypes.CDLL:
         "wc_coarse_units": (i32, [up, vp, i32, up, ctypes.POINTER(u64)]),
         "wc_inverse_coarse": (i32, [vp, vp, vp, up, i32, vp, vp, up, vp]),
         "wc_inverse_coarse_host": (i32, [vp, vp, vp, up, i32, vp, vp, up, vp]),
+        "wc_tol_levels_threshold": (i32, [vp, i32, u64, ctypes.c_double, ctypes.POINTER(ctypes.c_float),
+                                          ctypes.POINTER(ctypes.c_double)]),
+        "wc_forward_levels_tol": (i32, [vp, vp, i32, up, i32, vp, vp, vp, u64, vp, vp, vp, vp]),
+        "wc_forward_levels_tol_host": (i32, [vp, vp, i32, up, i32, vp, vp, vp, u64, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -323,6 +329,19 @@ class Context:
                                               float(keep), t, ctypes.c_void_p(d_payload), capacity,
                                               ctypes.c_void_p(d_offsets), ctypes.c_void_p(d_kept)))
 
+    def forward_levels_tol(self, d_cells: int, dtype: int, units, n: int, levels, tol, d_payload: int, capacity: int,
+                           d_offsets: int, d_kept: int, d_thresh: int | None = None, d_bound: int | None = None):
+        """wc_forward_levels with per-unit RMSE tolerances (n host doubles) in place
+        of keep / thresh: one threshold per level.  d_thresh (n x WC_MAX_LEVELS
+        floats, level l of unit u at u * WC_MAX_LEVELS + l - 1) / d_bound (n
+        doubles): optional device outputs."""
+        lv = _levels_array(levels, n)
+        t = _tol_array(tol, n)
+        self._check(self._L.wc_forward_levels_tol(self._h, ctypes.c_void_p(d_cells), dtype, units, n, lv.ctypes.data,
+                                                  t.ctypes.data, ctypes.c_void_p(d_payload), capacity,
+                                                  ctypes.c_void_p(d_offsets), ctypes.c_void_p(d_kept),
+                                                  ctypes.c_void_p(d_thresh or 0), ctypes.c_void_p(d_bound or 0)))
+
     def decompose_levels(self, d_cells: int, dtype: int, units, n: int, levels, d_flat: int):
         lv = _levels_array(levels, n)
         self._check(self._L.wc_decompose_levels(self._h, ctypes.c_void_p(d_cells), dtype, units, n, lv.ctypes.data,
@@ -436,6 +455,29 @@ class Context:
                                                 payload.ctypes.data, cap, offsets.ctypes.data, kept.ctypes.data,
                                                 thresh.ctypes.data, bound.ctypes.data, rmse.ctypes.data))
         return payload, offsets, kept[:n], thresh[:n], bound[:n], rmse[:n]
+
+    def forward_levels_tol_host(self, cells: np.ndarray, units, n: int, levels, tol, want_rmse: bool = True):
+        """wc_forward_levels_tol_host -> (payload, offsets, kept, thresh [n,
+        WC_MAX_LEVELS], bound, rmse); rmse is the actual RMSE of each unit's round
+        trip, taken on the device (None, and no round trip, without want_rmse)."""
+        c = np.ascontiguousarray(cells)
+        if c.dtype not in (np.float32, np.float64):
+            raise TypeError("cells must be float32 or float64")
+        dtype = WC_F64 if c.dtype == np.float64 else WC_F32
+        lv = _levels_array(levels, n)
+        t = _tol_array(tol, n)
+        cap = payload_bound(units, n)
+        payload = np.empty(cap, np.uint8)
+        offsets = np.zeros(n + 1, np.uint64)
+        kept = np.zeros(max(n, 1), np.uint32)
+        thresh = np.zeros((max(n, 1), WC_MAX_LEVELS), np.float32)
+        bound = np.zeros(max(n, 1), np.float64)
+        rmse = np.zeros(max(n, 1), np.float64) if want_rmse else None
+        self._check(self._L.wc_forward_levels_tol_host(self._h, c.ctypes.data, dtype, units, n, lv.ctypes.data,
+                                                       t.ctypes.data, payload.ctypes.data, cap, offsets.ctypes.data,
+                                                       kept.ctypes.data, thresh.ctypes.data, bound.ctypes.data,
+                                                       rmse.ctypes.data if want_rmse else None))
+        return payload, offsets, kept[:n], thresh[:n], bound[:n], rmse[:n] if want_rmse else None
 
     def forward_levels_host(self, cells: np.ndarray, units, n: int, levels, keep: float,
                             thresh: float | None = None):
@@ -614,6 +656,22 @@ def tol_threshold(counts: np.ndarray, ncoeff: int, tol: float):
     if rc:
         raise WaveletError(rc, "wc_tol_threshold: invalid argument")
     return float(t.value), float(b.value)
+
+
+def tol_levels_threshold(counts: np.ndarray, levels: int, ncoeff: int, tol: float):
+    """wc_tol_levels_threshold (host only): (fp32 thresholds of levels 1..L, model
+    RMSE bound) of the multi-level RMSE-tolerance rule on one unit's counts,
+    levels x WC_HIST_BINS uint64, level-major."""
+    h = np.ascontiguousarray(counts, dtype=np.uint64)
+    L = int(levels)
+    if 1 <= L <= WC_MAX_LEVELS and h.size != L * HIST_BINS:  # other L: the library refuses them
+        raise ValueError(f"counts must have levels x {HIST_BINS} bins")
+    t = (ctypes.c_float * WC_MAX_LEVELS)()
+    b = ctypes.c_double()
+    rc = load_library().wc_tol_levels_threshold(h.ctypes.data, L, int(ncoeff), float(tol), t, ctypes.byref(b))
+    if rc:
+        raise WaveletError(rc, "wc_tol_levels_threshold: invalid argument")
+    return [float(t[l]) for l in range(L)], float(b.value)
 
 
 def unit_payload(payload: np.ndarray, offsets: np.ndarray, kept: np.ndarray, u: int) -> bytes:

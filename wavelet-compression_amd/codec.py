@@ -120,25 +120,32 @@ def _pairs_need32(vals: np.ndarray) -> bool:
     return bool(vals.size and np.any(np.abs(vals.astype(np.float64)) > 32767))
 
 
-def compress_payloads(boxes: Sequence[np.ndarray], keep: float, device: int = 0, levels: int = 1):
+def compress_payloads(boxes: Sequence[np.ndarray], keep: float, device: int = 0, levels: int = 1, rmse=None):
     """Batched forward path: list of Box3D -> list of serialized payload bytes.
 
     One wc_forward_host_units call for the whole list (all units in one launch
     set, each uploaded from its own array: no packing copy on the host, as the
     C++ mirror's compress()).  levels > 1 (not a reference parameter): the
     opt-in multi-level transform, each box with the levels its dimensions admit
-    (capi.levels_for); such payloads carry ncoeff = -L in their headers."""
+    (capi.levels_for); such payloads carry ncoeff = -L in their headers.
+    rmse (not a reference parameter; None: the keep rule): the tolerated RMSE of
+    every box, one value or one per box, in place of keep, with one threshold
+    per level (wc_forward_levels_tol_host); boxes with cells need even
+    dimensions.  The payload format is the same."""
     dims = [_box_dims(b) for b in boxes]
     arrs = [np.ascontiguousarray(b, np.float32) for b in boxes]
     if not 1 <= int(levels) <= capi.WC_MAX_LEVELS:
         raise ValueError(f"levels: 1..{capi.WC_MAX_LEVELS}, not {levels!r}")
-    if levels > 1:
+    if levels > 1 or rmse is not None:
         units, n, extent = capi.make_units(dims)
         cells = np.zeros(max(extent, 1), np.float32)
         for i, a in enumerate(arrs):
             cells[units[i].cell_offset:units[i].cell_offset + a.size] = a.ravel()
         lv = [capi.levels_for(*d, levels) for d in dims]
-        payload, offsets, kept = context(device).forward_levels_host(cells, units, n, lv, keep)
+        if rmse is not None:
+            payload, offsets, kept = context(device).forward_levels_tol_host(cells, units, n, lv, rmse, want_rmse=False)[:3]
+        else:
+            payload, offsets, kept = context(device).forward_levels_host(cells, units, n, lv, keep)
         return [capi.unit_payload(payload, offsets, kept, i) for i in range(n)]
     units, n, _ = capi.make_units(dims)
     payload, offsets, kept = context(device).forward_host_units(arrs, units, n, keep)

@@ -85,11 +85,48 @@ std::vector<float> wavelet_decompose(const Box3D& box) {
 
 using namespace wavelet_amd;
 
+namespace {
+
+// Per component: the struct, and the .xz file (src/compressor.cpp:250-291) of
+// unit c's serialized bytes at payload + offsets[c]; the components' xz streams
+// are independent: encoded concurrently, or queued for the write-behind workers
+// (opt-in, xz_pool.h).
+std::vector<CompressedWavelet> write_components(const uint8_t* payload, const std::vector<uint64_t>& offsets,
+                                                const std::vector<uint32_t>& kept, const std::vector<int>& components,
+                                                int time, int level, int box_index, const std::string& compressed_dir) {
+    const int n = static_cast<int>(components.size());
+    std::vector<CompressedWavelet> out(n);
+    const bool behind = write_behind();
+    if (behind) note_write_behind_used();
+    parallel_for((size_t)n, behind ? 1 : std::min(n, host_threads()), [&](size_t c) {
+        std::string serialized(reinterpret_cast<const char*>(payload + offsets[c]), 20 + 8ull * kept[c]);
+        CompressedWavelet cw = deserialize_compressed_wavelet(serialized);
+        for (const auto& pr : cw.rle_encoded)
+            if (std::fabs((double)pr.second) > INT16_MAX) cw.need32 = true;  // src/compressor.cpp:229
+        const std::filesystem::path fname =
+            std::filesystem::path(compressed_dir) / ("compressed-wavelet-" + std::to_string(time) + "-" +
+                                                     std::to_string(level) + "-" + std::to_string(components[c]) +
+                                                     "-" + std::to_string(box_index) + ".xz");
+        if (behind) {
+            write_behind_submit(std::move(serialized), fname.string());
+        } else {
+            std::ofstream file(fname, std::ios::binary);
+            if (file.is_open()) {  // a failed open silently skips the file, as the reference does (:256-257)
+                const std::string xz = xz_compress(serialized);
+                file.write(xz.data(), (std::streamsize)xz.size());
+            }
+        }
+        out[c] = std::move(cw);
+    });
+    return out;
+}
+
+}  // namespace
+
 std::vector<CompressedWavelet> compress(multiBox3D& box, std::vector<int> components, double keep, int time,
                                         int level, int box_index, std::string compressed_dir) {
     const int n = static_cast<int>(components.size());
-    std::vector<CompressedWavelet> out;
-    if (n == 0) return out;
+    if (n == 0) return {};
     // box[0..n) (positional, src/compressor.cpp:203-206), each component from
     // its own Box3D storage: no packing copy on the host
     std::vector<wc_unit> units(n);
@@ -114,32 +151,39 @@ std::vector<CompressedWavelet> compress(multiBox3D& box, std::vector<int> compon
     check(ctx, wc_forward_host_units(ctx, cells.data(), WC_F32, units.data(), n, keep, t_payload.get(), cap,
                                      offsets.data(), kept.data()),
           "GPU forward");
-    // per component: the struct, and the .xz file (src/compressor.cpp:250-291);
-    // the components' xz streams are independent: encoded concurrently, or
-    // queued for the write-behind workers (opt-in, xz_pool.h)
-    out.resize(n);
-    const uint8_t* payload = t_payload.get();
-    const bool behind = write_behind();
-    if (behind) note_write_behind_used();
-    parallel_for((size_t)n, behind ? 1 : std::min(n, host_threads()), [&](size_t c) {
-        std::string serialized(reinterpret_cast<const char*>(payload + offsets[c]), 20 + 8ull * kept[c]);
-        CompressedWavelet cw = deserialize_compressed_wavelet(serialized);
-        for (const auto& pr : cw.rle_encoded)
-            if (std::fabs((double)pr.second) > INT16_MAX) cw.need32 = true;  // src/compressor.cpp:229
-        const std::filesystem::path fname =
-            std::filesystem::path(compressed_dir) / ("compressed-wavelet-" + std::to_string(time) + "-" +
-                                                     std::to_string(level) + "-" + std::to_string(components[c]) +
-                                                     "-" + std::to_string(box_index) + ".xz");
-        if (behind) {
-            write_behind_submit(std::move(serialized), fname.string());
-        } else {
-            std::ofstream file(fname, std::ios::binary);
-            if (file.is_open()) {  // a failed open silently skips the file, as the reference does (:256-257)
-                const std::string xz = xz_compress(serialized);
-                file.write(xz.data(), (std::streamsize)xz.size());
-            }
-        }
-        out[c] = std::move(cw);
-    });
-    return out;
+    return write_components(t_payload.get(), offsets, kept, components, time, level, box_index, compressed_dir);
+}
+
+std::vector<CompressedWavelet> wavelet_amd::compress_rmse(multiBox3D& box, std::vector<int> components, int levels,
+                                                          double rmse, int time, int level, int box_index,
+                                                          std::string compressed_dir) {
+    const int n = static_cast<int>(components.size());
+    if (n == 0) return {};
+    if (levels < 1 || levels > WC_MAX_LEVELS)
+        fatal("compress_rmse: levels " + std::to_string(levels) + " outside 1.." + std::to_string(WC_MAX_LEVELS));
+    // the host form takes one cell buffer: the components back to back, each start 4-element aligned
+    std::vector<wc_unit> units(n);
+    std::vector<int32_t> lv(n);
+    std::vector<double> tol(n, rmse);
+    uint64_t extent = 0;
+    for (int c = 0; c < n; ++c) {
+        const Box3D& b = box.at(c);
+        extent = (extent + 3) / 4 * 4;
+        units[c] = wc_unit{extent, (int32_t)b.width(), (int32_t)b.height(), (int32_t)b.depth(), 0};
+        lv[c] = wc_levels_for(units[c].nx, units[c].ny, units[c].nz, levels);
+        extent += b.data_size();
+    }
+    std::vector<float> cells(extent);
+    for (int c = 0; c < n; ++c)
+        if (box.at(c).data_size())
+            std::memcpy(cells.data() + units[c].cell_offset, box.at(c).data(), sizeof(float) * box.at(c).data_size());
+    const uint64_t cap = wc_payload_bound(units.data(), n);
+    std::unique_ptr<uint8_t[]> payload(new uint8_t[cap]);
+    std::vector<uint64_t> offsets(n + 1);
+    std::vector<uint32_t> kept(n);
+    wc_ctx* ctx = thread_ctx();
+    check(ctx, wc_forward_levels_tol_host(ctx, cells.data(), WC_F32, units.data(), n, lv.data(), tol.data(),
+                                          payload.get(), cap, offsets.data(), kept.data(), nullptr, nullptr, nullptr),
+          "GPU forward");
+    return write_components(payload.get(), offsets, kept, components, time, level, box_index, compressed_dir);
 }

@@ -6,7 +6,8 @@
 // launches.  No CPU fallback exists: every computing entry point launches HIP
 // kernels and fails with WC_ERR_HIP if the device or code object is absent.
 // The _host entry points are in wc_hostpipe.cpp (wc_forward_tol_host and the
-// host-only wc_tol_threshold: wc_tolhost.cpp).
+// host-only wc_tol_threshold: wc_tolhost.cpp; wc_forward_levels_tol_host:
+// wc_leveltolhost.cpp; the host-only wc_tol_levels_threshold: wc_leveltolrule.cpp).
 //
 // Forward path per batch (wc_forward), every unit shape: K1 k_transform{,_fast}
 // -> flat coefficients in HBM scratch (sparse staging: only the flagged
@@ -268,6 +269,71 @@ int run_levels(wc_ctx* c, const LevelWork& w, bool fwd, bool with_key, const uin
             e = launch_level(c->stream, false, du, w.lv[l - 2], w.nlv[l - 2], l - 1, coef, side, nullptr, bad);
     }
     return e == hipSuccess ? WC_OK : hip_fail(c, e, "level pass launch");
+}
+
+// RMSE tolerance on the multi-level transform (wc_leveltol.hip).  The call's
+// per-unit descriptors and its solo / split layout ride along with the level
+// work lists (upload_levels' extra blob):
+//   LtUnit[n] | items[nitems] | split_units[nsplit] | thresh[n * WC_MAX_LEVELS]
+// (8-B members first; the thresholds only when the caller passes no d_thresh).
+struct LevelTolWork {
+    std::vector<uint8_t> blob;
+    size_t o_items = 0, o_split = 0, o_thresh = 0;
+    uint32_t nitems = 0, nsplit = 0, chunk = 0;
+};
+
+void build_leveltol(const wc_ctx* c, int n, const int32_t* levels, const double* tol, bool own_thresh,
+                    LevelTolWork* t) {
+    const Plan& P = c->plan;
+    // as stage_tol: a unit of more than opt_tol_solo flat tiles is split into runs of `chunk` tiles
+    const uint32_t solo = (uint32_t)c->opt_tol_solo;
+    t->chunk = std::min<uint32_t>(solo, 8);
+    std::vector<LtUnit> lt(n);
+    std::vector<uint32_t> split;
+    std::vector<uint2> items;
+    for (int u = 0; u < n; ++u) {
+        const UnitDev& d = P.units[u];
+        lt[u] = {d.ncells ? rows_magic(d.nz) : 0, d.ncells ? rows_magic(d.ny) : 0, tol[u], (uint32_t)levels[u], kLtSolo};
+        if (d.nftiles <= solo) continue;
+        lt[u].slot = (uint32_t)split.size();
+        split.push_back((uint32_t)u);
+        for (uint32_t f = 0; f < d.nftiles; f += t->chunk) items.push_back(make_uint2((uint32_t)u, f));
+    }
+    t->nitems = (uint32_t)items.size();
+    t->nsplit = (uint32_t)split.size();
+    t->o_items = sizeof(LtUnit) * n;
+    t->o_split = t->o_items + sizeof(uint2) * items.size();
+    t->o_thresh = t->o_split + 4 * split.size();
+    t->blob.assign(t->o_thresh + (own_thresh ? sizeof(float) * WC_MAX_LEVELS * n : 0), 0);
+    std::memcpy(t->blob.data(), lt.data(), sizeof(LtUnit) * n);
+    if (!items.empty()) std::memcpy(t->blob.data() + t->o_items, items.data(), sizeof(uint2) * items.size());
+    if (!split.empty()) std::memcpy(t->blob.data() + t->o_split, split.data(), 4 * split.size());
+}
+
+// Between the level passes and the emit: the per-level bins and the pick of
+// every unit, then the mask pass that zeroes what the thresholds drop.
+int stage_leveltol(wc_ctx* c, int n, int maxl, const LevelTolWork& t, const uint8_t* d_blob, float* d_thresh,
+                   double* d_bound) {
+    const Plan& P = c->plan;
+    int rc;
+    hipError_t e;
+    const size_t bin_bytes = sizeof(uint32_t) * WC_HIST_BINS * (size_t)maxl * t.nsplit;
+    if (t.nsplit) {
+        if ((rc = ensure(c, c->tol_bins, bin_bytes))) return rc;
+        if ((e = hipMemsetAsync(c->tol_bins.p, 0, bin_bytes, c->stream)) != hipSuccess)
+            return hip_fail(c, e, "memset bins");
+    }
+    float* th = d_thresh ? d_thresh : (float*)const_cast<uint8_t*>(d_blob + t.o_thresh);
+    const UnitDev* du = (const UnitDev*)P.d_units.p;
+    const LtUnit* lt = (const LtUnit*)d_blob;
+    StageTimer timer(c, WC_STAGE_TOL);
+    e = launch_leveltol(c->stream, du, n, lt, (const uint2*)(d_blob + t.o_items), t.nitems, t.chunk,
+                        (const uint32_t*)(d_blob + t.o_split), t.nsplit, maxl, (const float*)c->coef.p,
+                        (uint32_t*)c->tol_bins.p, th, d_bound);
+    if (e == hipSuccess)
+        e = launch_leveltol_mask(c->stream, du, lt, (const FTile*)P.d_ftiles.p, (uint32_t)P.ftiles.size(),
+                                 (float*)c->coef.p, th);
+    return e == hipSuccess ? WC_OK : hip_fail(c, e, "level tolerance launch");
 }
 
 bool single_level(const int32_t* levels, int n) {
@@ -895,6 +961,43 @@ int wc_forward_levels(wc_ctx* c, const void* d_cells, int dtype, const wc_unit* 
         (rc = run_levels(c, w, true, !thresh)) || (rc = stage_emit(c, n, keep, thresh, d_payload, d_offsets, d_kept)))
         return rc;
     StageTimer t(c, WC_STAGE_LEVELS);
+    hipError_t e = launch_level_headers(c->stream, (const UnitDev*)c->plan.d_units.p, w.hdr, w.nhdr, d_payload);
+    return e == hipSuccess ? WC_OK : hip_fail(c, e, "level header launch");
+}
+
+// Multi-level forward with per-unit RMSE tolerances: wc_forward_levels' staging
+// and level passes, then the per-level bins, pick and mask pass on the final
+// array, the unchanged emit with threshold 0.0f on what the mask left, and the
+// header patch.  Leaves nothing staged.
+int wc_forward_levels_tol(wc_ctx* c, const void* d_cells, int dtype, const wc_unit* units, int n,
+                          const int32_t* levels, const double* tol, uint8_t* d_payload, uint64_t cap,
+                          uint64_t* d_offsets, uint32_t* d_kept, float* d_thresh, double* d_bound) {
+    if (!c) return WC_ERR_INVALID;
+    int rc;
+    if ((rc = validate_units(c, units, n))) return rc;
+    if (dtype != WC_F32 && dtype != WC_F64) return fail(c, WC_ERR_INVALID, "dtype");
+    if (n == 0) return WC_OK;
+    if (!d_cells || !d_payload || !d_offsets || !d_kept) return fail(c, WC_ERR_INVALID, "null buffer");
+    // an odd dimension passes validate_levels only at L = 1, where validate_tol refuses it
+    if ((rc = validate_levels(c, units, n, levels)) || (rc = validate_tol(c, units, n, tol))) return rc;
+    if (cap < wc_payload_bound(units, n)) return fail(c, WC_ERR_INVALID, "payload_capacity < wc_payload_bound");
+    if ((rc = check_aligned(c, d_cells, "cells")) || (rc = check_aligned(c, d_payload, "payload")) ||
+        (rc = check_aligned(c, d_offsets, "offsets", 8)) || (rc = check_aligned(c, d_kept, "kept", 4)) ||
+        (rc = check_aligned(c, d_thresh, "thresh", 4)) || (rc = check_aligned(c, d_bound, "bound", 8)))
+        return rc;
+    if ((rc = set_device(c)) || (rc = get_plan(c, units, n))) return rc;
+    if ((rc = ensure_scratch(c))) return rc;
+    LevelWork w;
+    LevelTolWork t;
+    build_leveltol(c, n, levels, tol, !d_thresh, &t);
+    const void* d_blob = nullptr;
+    const float zero = 0.0f;  // the mask pass has applied the thresholds: the emit keeps every non-zero
+    if ((rc = upload_levels(c, n, levels, &w, t.blob.data(), t.blob.size(), &d_blob)) ||
+        (rc = stage_transform(c, d_cells, dtype, 0.0, false)) || (rc = run_levels(c, w, true, false)) ||
+        (rc = stage_leveltol(c, n, w.maxl, t, (const uint8_t*)d_blob, d_thresh, d_bound)) ||
+        (rc = stage_emit(c, n, 0.0, &zero, d_payload, d_offsets, d_kept)))
+        return rc;
+    StageTimer timer(c, WC_STAGE_LEVELS);
     hipError_t e = launch_level_headers(c->stream, (const UnitDev*)c->plan.d_units.p, w.hdr, w.nhdr, d_payload);
     return e == hipSuccess ? WC_OK : hip_fail(c, e, "level header launch");
 }

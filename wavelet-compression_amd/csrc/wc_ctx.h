@@ -19,6 +19,10 @@
 //   wc_levelshost.cpp host side of the multi-level mode: wc_levels_for,
 //                    wc_payload_levels, the mode's argument checks and the
 //                    _levels_host entry points
+//   wc_leveltolrule.cpp / wc_leveltolhost.cpp  the RMSE tolerance on the
+//                    multi-level transform: the per-level selection rule (plain
+//                    C++, linked alone by tests/cpp/test_leveltol.cpp) and
+//                    wc_forward_levels_tol_host
 //   wc_coarsehost.cpp host side of the reduced-resolution inverse: wc_coarse_units,
 //                    the argument checks and wc_inverse_coarse_host
 #pragma once
@@ -79,6 +83,13 @@ hipError_t launch_level_headers(hipStream_t, const UnitDev*, const uint2* items,
 hipError_t launch_level_flat(hipStream_t, const UnitDev*, const FTile*, uint32_t ntiles, float* coef, float* flat,
                              int to_flat);
 uint32_t level_chunk_blocks();
+// wc_leveltol.hip: per-level bins + pick of the multi-level RMSE-tolerance mode,
+// and the mask pass that applies the per-level thresholds to the staged array
+hipError_t launch_leveltol(hipStream_t, const UnitDev*, int, const LtUnit*, const uint2* items, uint32_t nitems,
+                           uint32_t chunk, const uint32_t* split_units, uint32_t nsplit, int maxl, const float* coef,
+                           uint32_t* gbins, float* thresh, double* bound);
+hipError_t launch_leveltol_mask(hipStream_t, const UnitDev*, const LtUnit*, const FTile*, uint32_t ntiles, float* coef,
+                                const float* thresh);
 // wc_coarse.hip: the corner decode (over a prefix of the full plan's decode
 // tiles) into the compact corners, and the copy of the corners of the units with
 // r == L to their Box3D cells (over the derived plan's flat tiles)

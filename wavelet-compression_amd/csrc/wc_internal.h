@@ -101,6 +101,18 @@ struct CornerDesc {
 };
 static_assert(sizeof(CornerDesc) == 72, "descriptor of 8-B members first");
 
+// One unit of the multi-level RMSE-tolerance mode (wc_leveltol.hip).  Built per
+// call: the levels and tolerances are not part of a plan.
+struct LtUnit {
+    uint64_t dmagic;  // div_rows magic of D: row = floor(position / D)
+    uint64_t hmagic;  // div_rows magic of H: I = floor(row / H)
+    double tol;
+    uint32_t levels;  // L
+    uint32_t slot;    // kLtSolo, or the unit's index among the split units (its row of the global bins)
+};
+static_assert(sizeof(LtUnit) == 32, "descriptor of 8-B members first");
+constexpr uint32_t kLtSolo = 0xffffffffu;
+
 // Per-unit skip words (bad[u]) that k_decode<true> and k_decode_corner leave for
 // the launches after them: the level passes and k_inverse{,_fast}<true> skip a
 // unit unless its word is kUnitRun.
