@@ -528,6 +528,83 @@ int wc_inverse_coarse(wc_ctx* ctx, const uint8_t* d_payload, const uint64_t* d_o
 int wc_inverse_coarse_host(wc_ctx* ctx, const uint8_t* payload, const uint64_t* offsets, const wc_unit* units, int n,
                            const int32_t* levels, const int32_t* reduce, const wc_unit* out_units, float* out);
 
+/* Opt-in sub-box decode (not in the reference): the cells of a region of a box
+ * straight from its payload, reading only the coefficients the region depends
+ * on.  The transform is Haar on every level: a synthesis step writes cells 2m
+ * and 2m + 1 of a line from the low and the high coefficient m of that line and
+ * from nothing else, so a region aligned to 2^L depends on a small, exactly
+ * known subset of the coefficient array, and decoding that subset alone gives
+ * the bits of the full decode's crop.  It composes with the reduced-resolution
+ * decode: a region at 1/2^r resolution.
+ *
+ * Definition.  A unit W x H x D has L levels (its payload as wc_forward_levels
+ * writes it), a reduction r, 0 <= r <= L, and a region R in full-resolution
+ * cells.  For a unit with cells: 2^L divides W, H and D (for L = 1: even
+ * dimensions); 2^L divides every origin and extent of R; 0 <= x0 and x0 + nx <=
+ * W, likewise for y and z.  A region with a zero extent writes nothing.  A unit
+ * without cells needs an all-zero region.
+ * Result: a Box3D of (nx, ny, nz) >> r cells (w, h, d) with
+ *   out[x + w*(y + h*z)] = F_r((x0 >> r) + x, (y0 >> r) + y, (z0 >> r) + z),
+ * F_r being what wc_inverse_coarse gives at reduction r (F_0: wc_inverse_levels,
+ * or wc_inverse at L = 1), bit for bit.
+ * How: nothing of size W*H*D is written or read.  Write (W', H', D') =
+ * (W, H, D) >> r, L' = L - r, o = (x0, y0, z0) >> r, s = (nx, ny, nz) >> r.
+ * For the pair at flat position p < W*H*D, (I, J, K) from p = (I*H + J)*D + K:
+ *   1. Drop the pair unless I < W', J < H' and K < D' (the corner filter of the
+ *      reduced-resolution decode).
+ *   2. lvl = 0 if L' = 0; otherwise lvl = j* + 1, j* the largest j in 0..L'-1
+ *      with I < W' >> j, J < H' >> j and K < D' >> j.
+ *   3. Per axis, with n the axis' primed dimension, c its coordinate, o and s
+ *      its origin and extent: if lvl >= 1 and c >= n >> lvl (high band),
+ *      q = c - (n >> lvl) - (o >> lvl) and i = q + (s >> lvl); otherwise
+ *      q = c - (o >> lvl) and i = q.  Keep the pair iff 0 <= q < s >> lvl on all
+ *      three axes.
+ *   4. Store the value at C[(i_x*s_y + i_y)*s_z + i_z] of a zeroed compact array.
+ * C is the flat array of an s_x x s_y x s_z unit with L' levels: for L' >= 1
+ * the result is its multi-level inverse, for L' = 0 C read as a Box3D.  No kept
+ * pair sits at or past `end`, one past the flat position of the largest needed
+ * (I, J, K); per axis that coordinate is (n >> 1) + (o >> 1) + (s >> 1) - 1 for
+ * L' >= 1 and o + s - 1 for L' = 0.  Pair tiles past `end` leave at once.
+ * Equalities: R = the whole box gives wc_inverse_coarse bit for bit (with r = 0
+ * wc_inverse_levels); any R gives the crop of those.
+ *
+ *   wc_region_align: host-only; *aligned = the smallest region aligned to
+ *     2^levels that contains *want inside the box nx x ny x nz (an axis of zero
+ *     extent stays empty, at its origin rounded down).  WC_ERR_INVALID for null
+ *     pointers, a region not inside the box, levels outside 1..WC_MAX_LEVELS or
+ *     a box with cells whose dimensions 2^levels does not divide.
+ *   wc_region_units: host-only; out[u] carries regions[u]'s extents >>
+ *     reduce[u] (reduce NULL = all 0), packed as wc_coarse_units packs.  `units`
+ *     is not read beyond the null check.  WC_ERR_INVALID for null pointers,
+ *     negative extents or a reduce outside 0..WC_MAX_LEVELS.
+ *   wc_inverse_region: units describe the payloads at full size (cell_offset
+ *     ignored); levels (NULL = all 1), reduce (NULL = all 0) and regions are on
+ *     the HOST and consumed before the call returns.  out_units[u] must carry
+ *     exactly the extents >> reduce[u]; its cell_offset is the caller's choice
+ *     (any element alignment; d_out itself 16-byte aligned).  Asynchronous;
+ *     malformed payloads as in wc_inverse_coarse: a header that disagrees raises
+ *     WC_ERR_FORMAT at the next wc_synchronize, the unit's output cells stay
+ *     untouched and the other units decode; a negative run raises the same error
+ *     and writes nothing outside the unit's own scratch and output range.  A
+ *     unit whose region has no cells reads nothing, its header included.
+ *   wc_inverse_region_host: host buffers; levels = NULL reads each L from its
+ *     header; the unit runs go one after another; only the regions' cells cross
+ *     back.
+ * A reduce outside 0..levels[u], a region that is not inside the box or not
+ * aligned to 2^L, a dimension 2^L does not divide, an out_units entry with other
+ * dims or reserved != 0, or a null buffer: WC_ERR_INVALID naming the unit,
+ * before anything is launched; outputs stay untouched. */
+typedef struct wc_region { int32_t x0, y0, z0, nx, ny, nz; } wc_region;  /* full-resolution cells */
+int wc_region_align(int32_t nx, int32_t ny, int32_t nz, int levels, const wc_region* want, wc_region* aligned);
+int wc_region_units(const wc_unit* units, const wc_region* regions, const int32_t* reduce, int n, wc_unit* out,
+                    uint64_t* extent);
+int wc_inverse_region(wc_ctx* ctx, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                      const int32_t* levels, const int32_t* reduce, const wc_region* regions, const wc_unit* out_units,
+                      float* d_out);
+int wc_inverse_region_host(wc_ctx* ctx, const uint8_t* payload, const uint64_t* offsets, const wc_unit* units, int n,
+                           const int32_t* levels, const int32_t* reduce, const wc_region* regions,
+                           const wc_unit* out_units, float* out);
+
 /* Transform only: cells -> flat fp32 coefficients (x-slowest order), written
  * at the same element offsets as the cells (d_flat has the cell buffer's extent). */
 int wc_decompose(wc_ctx* ctx, const void* d_cells, int dtype, const wc_unit* units, int n,

@@ -3,6 +3,7 @@
 // reference's unit tests can be restated against this library.
 #pragma once
 
+#include <array>
 #include <string>
 #include <utility>
 #include <vector>
@@ -35,6 +36,17 @@ std::string xz_decompress(const std::string& xz);
 // 2^reduce must divide W, H and D; otherwise it exits with a message, as the
 // other read errors do.
 Box3D decompress_coarse(const std::string& file_path, int reduce);
+
+// The cells [lo, hi) of decompress()'s box (hi exclusive, x, y, z in cells of the
+// full box), or with reduce = r >= 1 the cells [lo >> r, ceil(hi / 2^r)) of
+// decompress_coarse()'s (GPU, wc_inverse_region_host; not in the reference).  The
+// region is rounded outward to multiples of 2^L, L the file's levels
+// (wc_region_align), decoded from the coefficients it depends on alone, and
+// cropped on the host; the bits are those of the crop of the full decode.  A
+// region that is empty or not inside the box, dimensions that 2^L does not
+// divide, or a reduce beyond the file's levels: it exits with a message, as the
+// other read errors do.
+Box3D decompress_region(const std::string& file_path, std::array<int, 3> lo, std::array<int, 3> hi, int reduce = 0);
 
 // compress() with a tolerated RMSE in place of keep (GPU, wc_forward_levels_tol_host;
 // not in the reference): every component of the box is transformed with the levels

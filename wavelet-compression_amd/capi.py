@@ -35,6 +35,7 @@ EXPORTED = (
     "wc_inverse_flat_levels", "wc_inverse_levels", "wc_forward_levels_host", "wc_inverse_levels_host",
     "wc_coarse_units", "wc_inverse_coarse", "wc_inverse_coarse_host",
     "wc_tol_levels_threshold", "wc_forward_levels_tol", "wc_forward_levels_tol_host",
+    "wc_region_align", "wc_region_units", "wc_inverse_region", "wc_inverse_region_host",
 )
 WC_MAX_LEVELS = 4  # levels of the opt-in multi-level transform (1 = the reference's codec)
 WC_LTOL_SHIFT = 24  # bins between the walks of two adjacent levels in the multi-level RMSE-tolerance rule
@@ -64,6 +65,12 @@ class WcUnit(ctypes.Structure):
                 ("ny", ctypes.c_int32), ("nz", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class WcRegion(ctypes.Structure):
+    """wc_region: origin and extent of a sub-box in full-resolution cells."""
+    _fields_ = [("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("z0", ctypes.c_int32),
+                ("nx", ctypes.c_int32), ("ny", ctypes.c_int32), ("nz", ctypes.c_int32)]
+
+
 class WaveletError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"wavelet_amd error {code}: {msg}")
@@ -87,6 +94,7 @@ def load_library() -> ctypes.CDLL:
     L = ctypes.CDLL(os.environ.get("WCAMD_LIB") or str(LIB_PATH))
     vp, u64, i32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int
     up = ctypes.POINTER(WcUnit)
+    rp = ctypes.POINTER(WcRegion)
     sigs = {
         "wc_ctx_create": (i32, [i32, ctypes.POINTER(vp)]),
         "wc_ctx_destroy": (None, [vp]),
@@ -143,6 +151,10 @@ def load_library() -> ctypes.CDLL:
                                           ctypes.POINTER(ctypes.c_double)]),
         "wc_forward_levels_tol": (i32, [vp, vp, i32, up, i32, vp, vp, vp, u64, vp, vp, vp, vp]),
         "wc_forward_levels_tol_host": (i32, [vp, vp, i32, up, i32, vp, vp, vp, u64, vp, vp, vp, vp, vp]),
+        "wc_region_align": (i32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, i32, rp, rp]),
+        "wc_region_units": (i32, [up, rp, vp, i32, up, ctypes.POINTER(u64)]),
+        "wc_inverse_region": (i32, [vp, vp, vp, up, i32, vp, vp, rp, up, vp]),
+        "wc_inverse_region_host": (i32, [vp, vp, vp, up, i32, vp, vp, rp, up, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -368,6 +380,19 @@ class Context:
                                               n, None if lv is None else lv.ctypes.data, rd.ctypes.data, out_units,
                                               ctypes.c_void_p(d_out)))
 
+    def inverse_region(self, d_payload: int, d_offsets: int, units, n: int, levels, reduce, regions, out_units,
+                       d_out: int):
+        """wc_inverse_region: the cells of regions[u] of unit u at 1/2^reduce[u]
+        resolution into out_units[u] (region_units, or the caller's offsets with
+        the same dims).  levels None: all 1; reduce None: all 0; regions: a
+        WcRegion array or n (x0, y0, z0, nx, ny, nz) rows."""
+        lv = None if levels is None else _levels_array(levels, n)
+        rd = None if reduce is None else _levels_array(reduce, n)
+        self._check(self._L.wc_inverse_region(self._h, ctypes.c_void_p(d_payload), ctypes.c_void_p(d_offsets), units,
+                                              n, None if lv is None else lv.ctypes.data,
+                                              None if rd is None else rd.ctypes.data, make_regions(regions, n),
+                                              out_units, ctypes.c_void_p(d_out)))
+
     def decompose(self, d_cells: int, dtype: int, units, n: int, d_flat: int):
         self._check(self._L.wc_decompose(self._h, ctypes.c_void_p(d_cells), dtype, units, n,
                                          ctypes.c_void_p(d_flat)))
@@ -529,6 +554,25 @@ class Context:
                                                    out.ctypes.data))
         return out[:extent]
 
+    def inverse_region_host(self, payload: np.ndarray, offsets: np.ndarray, units, n: int, reduce, regions, out_units,
+                            extent: int, levels=None, out=None):
+        """wc_inverse_region_host -> float32[extent] region boxes at out_units'
+        offsets; levels None: each unit's L is read from its payload header;
+        reduce None: all 0."""
+        p = np.ascontiguousarray(payload, dtype=np.uint8)
+        o = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lv = None if levels is None else _levels_array(levels, n)
+        rd = None if reduce is None else _levels_array(reduce, n)
+        if out is None:
+            out = np.zeros(max(extent, 1), np.float32)
+        elif out.dtype != np.float32 or out.size < extent or not out.flags.c_contiguous:
+            raise ValueError("out: contiguous float32[>= extent]")
+        self._check(self._L.wc_inverse_region_host(self._h, p.ctypes.data, o.ctypes.data, units, n,
+                                                   None if lv is None else lv.ctypes.data,
+                                                   None if rd is None else rd.ctypes.data, make_regions(regions, n),
+                                                   out_units, out.ctypes.data))
+        return out[:extent]
+
     def forward_host_units(self, boxes, units, n: int, keep: float):
         """wc_forward_host_units: unit u's cells from boxes[u] (its own host
         array, all float32 or all float64) -> (payload, offsets, kept)."""
@@ -631,6 +675,42 @@ def coarse_units(units, n: int, reduce):
     rc = load_library().wc_coarse_units(units, rd.ctypes.data, n, out, ctypes.byref(ext))
     if rc:
         raise WaveletError(rc, "wc_coarse_units: negative dims or a reduce outside 0..WC_MAX_LEVELS")
+    return out, int(ext.value)
+
+
+def make_regions(regions, n: int):
+    """A wc_region array from n (x0, y0, z0, nx, ny, nz) rows (a WcRegion array passes through)."""
+    if isinstance(regions, ctypes.Array) and regions._type_ is WcRegion:
+        return regions
+    rows = [tuple(int(v) for v in g) for g in regions]
+    if len(rows) != n or any(len(g) != 6 for g in rows):
+        raise ValueError(f"regions: {n} rows of (x0, y0, z0, nx, ny, nz)")
+    return (WcRegion * max(n, 1))(*[WcRegion(*g) for g in rows])
+
+
+def region_align(dims, levels: int, region):
+    """wc_region_align (host only): the smallest region aligned to 2^levels that
+    contains region = (x0, y0, z0, nx, ny, nz) inside the box dims = (W, H, D),
+    as the same kind of tuple."""
+    want, got = WcRegion(*[int(v) for v in region]), WcRegion()
+    rc = load_library().wc_region_align(int(dims[0]), int(dims[1]), int(dims[2]), int(levels), ctypes.byref(want),
+                                        ctypes.byref(got))
+    if rc:
+        raise WaveletError(rc, "wc_region_align: a region outside the box, levels outside 1..WC_MAX_LEVELS or "
+                               "dimensions that 2^levels does not divide")
+    return (got.x0, got.y0, got.z0, got.nx, got.ny, got.nz)
+
+
+def region_units(units, n: int, regions, reduce=None):
+    """wc_region_units (host only): (out_units, extent) of the regions' boxes:
+    unit u's extents >> reduce[u], packed back to back with each start rounded up to 4."""
+    rd = None if reduce is None else _levels_array(reduce, n)
+    out = (WcUnit * max(n, 1))()
+    ext = ctypes.c_uint64()
+    rc = load_library().wc_region_units(units, make_regions(regions, n), None if rd is None else rd.ctypes.data, n, out,
+                                        ctypes.byref(ext))
+    if rc:
+        raise WaveletError(rc, "wc_region_units: negative extents or a reduce outside 0..WC_MAX_LEVELS")
     return out, int(ext.value)
 
 

@@ -209,7 +209,36 @@ def _coarse_dims(payloads: Sequence[bytes], dims, coarsen) -> list:
     return [(W >> r, H >> r, D >> r) for W, H, D in dims]
 
 
-def decompress_payloads(payloads: Sequence[bytes], device: int = 0, coarsen: int = 0) -> List[np.ndarray]:
+def _aligned_regions(payloads: Sequence[bytes], dims, region) -> tuple:
+    """region = ((x0, y0, z0), (x1, y1, z1)), hi exclusive, in cells of the full
+    boxes -> (lo, hi, each payload's region rounded outward to its 2^L as
+    (x0, y0, z0, nx, ny, nz)), after the checks that need no device: a non-empty
+    region inside every box, 2^L dividing every box's dims (ValueError)."""
+    try:
+        lo, hi = (tuple(int(v) for v in region[0]), tuple(int(v) for v in region[1]))
+        ok = len(region) == 2 and len(lo) == 3 and len(hi) == 3
+    except (TypeError, ValueError, IndexError):
+        ok = False
+    if not ok:
+        raise ValueError(f"region: ((x0, y0, z0), (x1, y1, z1)), not {region!r}")
+    if any(b <= a for a, b in zip(lo, hi)):
+        raise ValueError(f"region {lo}..{hi} is empty")
+    out = []
+    for i, (p, (W, H, D)) in enumerate(zip(payloads, dims)):
+        if any(a < 0 for a in lo) or hi[0] > W or hi[1] > H or hi[2] > D:
+            raise ValueError(f"payload {i} ({W}x{H}x{D}): region {lo}..{hi} is not inside the box")
+        nc = int(np.frombuffer(p[12:16], "<i4")[0])
+        L = 1 if nc >= 0 else -nc
+        if not 1 <= L <= capi.WC_MAX_LEVELS:
+            raise ValueError(f"payload {i}: not a payload header")
+        if (W | H | D) & ((1 << L) - 1):
+            raise ValueError(f"payload {i} ({W}x{H}x{D}): a region decode of {L} level(s) needs W, H and D "
+                             f"divisible by {1 << L}")
+        out.append(capi.region_align((W, H, D), L, lo + tuple(b - a for a, b in zip(lo, hi))))
+    return lo, hi, out
+
+
+def decompress_payloads(payloads: Sequence[bytes], device: int = 0, coarsen: int = 0, region=None) -> List[np.ndarray]:
     """Batched inverse path: serialized payloads -> Box3D arrays (one wc_inverse_host
     call; wc_inverse_levels_host, which reads each payload's levels from its
     header, when some payload is a multi-level one: ncoeff < 0).
@@ -218,7 +247,15 @@ def decompress_payloads(payloads: Sequence[bytes], device: int = 0, coarsen: int
     shape (D >> r, H >> r, W >> r), each cell the mean of a 2^r-cube of the full
     box up to fp32 rounding, decoded from the low-pass corner of its
     coefficients alone (wc_inverse_coarse_host).  Works on reference-format
-    payloads (one level) with r = 1 and even dims."""
+    payloads (one level) with r = 1 and even dims.
+
+    region = ((x0, y0, z0), (x1, y1, z1)) (not a reference parameter): only the
+    cells [lo, hi) of every box, shape (z1 - z0, y1 - y0, x1 - x0); with coarsen
+    = r the cells [lo >> r, ceil(hi / 2^r)) of the coarse box.  Any region
+    inside the box: it is rounded outward to multiples of 2^L (L the payload's
+    levels, which must divide the box's dims), decoded from the coefficients it
+    depends on alone (wc_inverse_region_host) and cropped here.  The bits are
+    those of the crop of the full decode."""
     dims = []
     multi = False
     for p in payloads:
@@ -226,6 +263,8 @@ def decompress_payloads(payloads: Sequence[bytes], device: int = 0, coarsen: int
         dims.append((int(h[0]), int(h[1]), int(h[2])))
         multi |= int(h[3]) < 0
     cdims = _coarse_dims(payloads, dims, coarsen)
+    if region is not None:
+        lo, hi, regions = _aligned_regions(payloads, dims, region)
     units, n, extent = capi.make_units(dims)
     offsets = np.zeros(max(n, 1), np.uint64)
     cur = 4
@@ -236,6 +275,20 @@ def decompress_payloads(payloads: Sequence[bytes], device: int = 0, coarsen: int
     for i, p in enumerate(payloads):
         o = int(offsets[i])
         buf[o:o + len(p)] = np.frombuffer(p, np.uint8)
+    if region is not None:
+        r = int(coarsen)
+        out_units, extent = capi.region_units(units, n, regions, r)
+        flat = context(device).inverse_region_host(buf, offsets, units, n, r, regions, out_units, extent)
+        up = (1 << r) - 1
+        out = []
+        for i, g in enumerate(regions):
+            w, h, d = g[3] >> r, g[4] >> r, g[5] >> r
+            o = out_units[i].cell_offset
+            a = [(lo[k] >> r) - (g[k] >> r) for k in range(3)]
+            m = [((hi[k] + up) >> r) - (lo[k] >> r) for k in range(3)]
+            box = flat[o:o + w * h * d].reshape(d, h, w)
+            out.append(box[a[2]:a[2] + m[2], a[1]:a[1] + m[1], a[0]:a[0] + m[0]].copy())
+        return out
     if coarsen:
         out_units, extent = capi.coarse_units(units, n, int(coarsen))
         flat = context(device).inverse_coarse_host(buf, offsets, units, n, int(coarsen), out_units, extent)
@@ -252,10 +305,10 @@ def decompress_payloads(payloads: Sequence[bytes], device: int = 0, coarsen: int
 
 
 def decompress(file_path, time: int = 0, level: int = 0, component: int = 0, box_idx: int = 0,
-               coarsen: int = 0) -> np.ndarray:
+               coarsen: int = 0, region=None) -> np.ndarray:
     """src/decompressor.cpp:238-255 (only file_path is used, as in the reference).
-    coarsen (not a reference parameter): see decompress_payloads."""
-    return decompress_payloads([read_compressed_payload(file_path)], coarsen=coarsen)[0]
+    coarsen, region (not reference parameters): see decompress_payloads."""
+    return decompress_payloads([read_compressed_payload(file_path)], coarsen=coarsen, region=region)[0]
 
 
 def inverse_wavelet_decompose(flat, x: int, y: int, z: int) -> np.ndarray:

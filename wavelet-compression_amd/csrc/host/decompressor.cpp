@@ -145,3 +145,50 @@ Box3D wavelet_amd::decompress_coarse(const std::string& file_path, int reduce) {
     check(c, wc_inverse_coarse_host(c, buf.data(), &off, &u, 1, nullptr, &r, &o, out.data()), "GPU coarse decompress");
     return out;
 }
+
+Box3D wavelet_amd::decompress_region(const std::string& file_path, std::array<int, 3> lo, std::array<int, 3> hi,
+                                     int reduce) {
+    flush_writes(file_path);
+    const std::string payload = xz_decompress(read_file(file_path));
+    if (payload.size() < 20) fatal("Deserialization failed: payload shorter than its header");
+    int32_t hdr[5];
+    std::memcpy(hdr, payload.data(), sizeof hdr);
+    if (hdr[0] < 0 || hdr[1] < 0 || hdr[2] < 0) fatal("Deserialization failed: negative dimensions");
+    int L = 0;
+    if (wc_payload_levels(reinterpret_cast<const uint8_t*>(payload.data()), 20, &L) != WC_OK)
+        fatal("Deserialization failed: malformed payload header");
+    if (reduce < 0 || reduce > L)
+        fatal("decompress_region: reduce " + std::to_string(reduce) + " outside 0.." + std::to_string(L));
+    const std::string box = std::to_string(hdr[0]) + "x" + std::to_string(hdr[1]) + "x" + std::to_string(hdr[2]);
+    for (int a = 0; a < 3; ++a)
+        if (lo[a] < 0 || hi[a] <= lo[a] || hi[a] > hdr[a])
+            fatal("decompress_region: the region must be non-empty and inside the box " + box);
+    const wc_region want{lo[0], lo[1], lo[2], hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
+    wc_region g;
+    if (wc_region_align(hdr[0], hdr[1], hdr[2], L, &want, &g) != WC_OK)
+        fatal("decompress_region: " + std::to_string(L) + " level(s) need W, H and D of " + box + " divisible by " +
+              std::to_string(1 << L));
+    const wc_unit u{0, hdr[0], hdr[1], hdr[2], 0};
+    const int32_t r = reduce, lv = L;
+    wc_unit o;
+    uint64_t extent = 0;
+    wc_region_units(&u, &g, &r, 1, &o, &extent);
+    std::vector<float> cells(extent);
+    std::vector<uint8_t> buf(payload.size() + 8);
+    std::memcpy(buf.data() + 4, payload.data(), payload.size());
+    const uint64_t off = 4;
+    wc_ctx* c = thread_ctx();
+    check(c, wc_inverse_region_host(c, buf.data(), &off, &u, 1, &lv, &r, &g, &o, cells.data()), "GPU region decompress");
+    // the crop [lo >> r, ceil(hi / 2^r)) of the aligned region's box
+    const int up = (1 << r) - 1;
+    const int a0[3] = {(lo[0] >> r) - (g.x0 >> r), (lo[1] >> r) - (g.y0 >> r), (lo[2] >> r) - (g.z0 >> r)};
+    const int n[3] = {((hi[0] + up) >> r) - (lo[0] >> r), ((hi[1] + up) >> r) - (lo[1] >> r),
+                      ((hi[2] + up) >> r) - (lo[2] >> r)};
+    Box3D out(n[0], n[1], n[2]);
+    for (int z = 0; z < n[2]; ++z)
+        for (int y = 0; y < n[1]; ++y)
+            std::memcpy(out.data() + (size_t)n[0] * (y + (size_t)n[1] * z),
+                        cells.data() + a0[0] + (size_t)o.nx * ((a0[1] + y) + (size_t)o.ny * (a0[2] + z)),
+                        sizeof(float) * n[0]);
+    return out;
+}

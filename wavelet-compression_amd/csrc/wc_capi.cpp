@@ -19,6 +19,7 @@
 // payloads; units that are not row-indexable: k_decode -> dense flat scratch
 // -> K6 k_inverse{,_fast}.
 #include "wc_ctx.h"
+#include "wc_regionmap.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1204,6 +1205,145 @@ int wc_inverse_coarse(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_off
     c->err_check_pending = true;  // malformed payloads surface at the next wc_synchronize
     if (w.maxl >= 2 && (rc = run_levels(c, w, false, false, bad))) return rc;
     if (!any_run) return WC_OK;  // every unit's corner was its result
+    StageTimer t(c, WC_STAGE_INVERSE);
+    e = launch_inverse(c->stream, (const float*)c->coef.p, 0, (const UnitDev*)P.d_units.p, (const XTile*)P.d_ixtiles.p,
+                       P.ign, P.lds_inverse, P.ifast, P.lds_fast, d_out, bad);
+    return e == hipSuccess ? WC_OK : hip_fail(c, e, "inverse launch");
+}
+
+// Sub-box inverse (wc_region.hip).  The two plans of wc_inverse_coarse: the one
+// of the full-size units gives the pair tiles of the region decode and their
+// look-back granules; the one of out_units (the derived units: the regions'
+// extents >> r) places each compact unit in the coefficient scratch and runs the
+// L - r levels and the one-level inverse on it.  Both are dense plans
+// (WC_OPT_INVERSE_ROWS = 0) and stay in the plan cache.
+int wc_inverse_region(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                      const int32_t* levels, const int32_t* reduce, const wc_region* regions, const wc_unit* out_units,
+                      float* d_out) {
+    if (!c) return WC_ERR_INVALID;
+    int rc;
+    if ((rc = validate_units(c, units, n))) return rc;
+    if (n == 0) return WC_OK;
+    if (!d_payload || !d_offsets || !regions || !out_units || !d_out) return fail(c, WC_ERR_INVALID, "null buffer");
+    std::vector<int32_t> ones, zeros;
+    if (!levels) {
+        ones.assign(n, 1);
+        levels = ones.data();
+    }
+    if (!reduce) {
+        zeros.assign(n, 0);
+        reduce = zeros.data();
+    }
+    if ((rc = validate_levels(c, units, n, levels)) ||
+        (rc = validate_region(c, units, n, levels, reduce, regions, out_units)))
+        return rc;
+    if ((rc = check_aligned(c, d_payload, "payload")) || (rc = check_aligned(c, d_offsets, "offsets", 8)) ||
+        (rc = check_aligned(c, d_out, "out")))
+        return rc;
+    if ((rc = set_device(c))) return rc;
+    // the full units' plan: the decoder ignores their cell offsets, so the key carries none
+    std::vector<wc_unit> full(units, units + n);
+    for (wc_unit& u : full) u.cell_offset = 0;
+    std::vector<RegionDesc> desc(n);
+    std::vector<int32_t> rest(n);  // levels of the compact unit: L - r (1 for r == L, which runs nothing)
+    bool any_direct = false, any_run = false;
+    uint32_t maxt = 0;  // the batch's largest ceil(end / kFlatTile): no tile index at or past it has work
+    for (int u = 0; u < n; ++u) {
+        const wc_unit& f = units[u];
+        const wc_unit& o = out_units[u];
+        const wc_region& g = regions[u];
+        RegionDesc& d = desc[u];
+        const int L = levels[u], r = reduce[u];
+        std::memset(&d, 0, sizeof d);  // end = 0: no tile reads the rest
+        rest[u] = std::max(1, L - r);
+        d.direct = r == L ? 1u : 0u;
+        d.out_off = o.cell_offset;
+        d.W = f.nx;
+        d.H = f.ny;
+        d.D = f.nz;
+        const uint64_t cells = (uint64_t)f.nx * f.ny * f.nz;
+        d.want = L >= 2 ? -L : (int32_t)cells;
+        if (!cells) continue;
+        d.w = (uint32_t)(f.nx >> r);
+        d.h = (uint32_t)(f.ny >> r);
+        d.d = (uint32_t)(f.nz >> r);
+        d.L = (uint32_t)(L - r);
+        d.ox = (uint32_t)(g.x0 >> r);
+        d.oy = (uint32_t)(g.y0 >> r);
+        d.oz = (uint32_t)(g.z0 >> r);
+        d.sx = (uint32_t)o.nx;
+        d.sy = (uint32_t)o.ny;
+        d.sz = (uint32_t)o.nz;
+        d.dmagic = rows_magic(f.nz);
+        d.hmagic = rows_magic(f.ny);
+        d.end = (uint32_t)region_end(d.w, d.h, d.d, d.L, d.ox, d.oy, d.oz, d.sx, d.sy, d.sz, (uint32_t)f.ny,
+                                     (uint32_t)f.nz);  // <= W*H*D < 2^31
+        if (!d.end) continue;  // a region without cells
+        maxt = std::max(maxt, (d.end - 1) / (uint32_t)kFlatTile + 1);
+        any_direct |= d.direct != 0;
+        any_run |= d.direct == 0;
+    }
+    const bool rows = c->opt_inv_rows;
+    c->opt_inv_rows = false;  // the plans' key holds it (wc_inverse_levels)
+    const FTile* dtiles = nullptr;
+    uint32_t ndt = 0;
+    size_t dstate = 0;
+    if ((rc = get_plan(c, full.data(), n)) == WC_OK) {
+        const Plan& F = c->plan;
+        dtiles = (const FTile*)F.d_dtiles.p;  // the plan moves into the cache below: its buffers stay
+        dstate = decode_state_bytes(F);
+        // dtiles is ordered by tile index, then unit: the tiles below maxt are a prefix of it
+        for (int u = 0; u < n; ++u) {
+            desc[u].dt_begin = F.units[u].dt_begin;
+            ndt += std::min(F.units[u].ndt, maxt);
+        }
+        rc = get_plan(c, out_units, n);
+    }
+    c->opt_inv_rows = rows;
+    if (rc || (rc = ensure_scratch(c)) || (rc = ensure(c, c->state, dstate))) return rc;
+    const Plan& P = c->plan;
+    // the descriptors, then (for k_corner_box) the CornerDesc of every unit: its corner is the compact unit
+    std::vector<uint8_t> blob(sizeof(RegionDesc) * n + (any_direct ? sizeof(CornerDesc) * n : 0));
+    for (int u = 0; u < n; ++u) desc[u].dst_off = P.units[u].coef_off;
+    std::memcpy(blob.data(), desc.data(), sizeof(RegionDesc) * n);
+    if (any_direct) {
+        std::vector<CornerDesc> cd(n);
+        for (int u = 0; u < n; ++u) {
+            std::memset(&cd[u], 0, sizeof(CornerDesc));
+            cd[u].dst_off = desc[u].dst_off;
+            cd[u].out_off = desc[u].out_off;
+            cd[u].w = desc[u].sx;
+            cd[u].h = desc[u].sy;
+            cd[u].d = desc[u].sz;
+            cd[u].direct = desc[u].direct;
+        }
+        std::memcpy(blob.data() + sizeof(RegionDesc) * n, cd.data(), sizeof(CornerDesc) * n);
+    }
+    LevelWork w;
+    const void* d_desc = nullptr;
+    if ((rc = upload_levels(c, n, rest.data(), &w, blob.data(), blob.size(), &d_desc))) return rc;
+    DecodeState ds;
+    hipError_t e = decode_state(c, n, dstate, true, &ds);
+    if (e != hipSuccess) return hip_fail(c, e, "memset");
+    uint32_t* bad = (uint32_t*)c->npairs.p;  // per-unit "skip" words, as in wc_inverse_levels
+    {
+        StageTimer t(c, WC_STAGE_DECODE);
+        // the compact units: positions without a pair must read as zeros
+        if (P.coef_extent && (e = hipMemsetAsync(c->coef.p, 0, sizeof(float) * P.coef_extent, c->stream)) != hipSuccess)
+            return hip_fail(c, e, "memset");
+        e = launch_decode_region(c->stream, (const RegionDesc*)d_desc, dtiles, ndt, d_payload, d_offsets, ds.ticket,
+                                 ds.status, (float*)c->coef.p, (uint32_t*)c->errflag.p, ds.ordered, bad);
+        // the units with r == L: their compact units are their cells
+        if (e == hipSuccess && any_direct)
+            e = launch_corner_box(c->stream,
+                                  (const CornerDesc*)((const uint8_t*)d_desc + sizeof(RegionDesc) * n),
+                                  (const FTile*)P.d_ftiles.p, (uint32_t)P.ftiles.size(), (const float*)c->coef.p,
+                                  d_out, bad);
+        if (e != hipSuccess) return hip_fail(c, e, "region decode launch");
+    }
+    c->err_check_pending = true;  // malformed payloads surface at the next wc_synchronize
+    if (w.maxl >= 2 && (rc = run_levels(c, w, false, false, bad))) return rc;
+    if (!any_run) return WC_OK;  // every compact unit was its result, or no region had cells
     StageTimer t(c, WC_STAGE_INVERSE);
     e = launch_inverse(c->stream, (const float*)c->coef.p, 0, (const UnitDev*)P.d_units.p, (const XTile*)P.d_ixtiles.p,
                        P.ign, P.lds_inverse, P.ifast, P.lds_fast, d_out, bad);

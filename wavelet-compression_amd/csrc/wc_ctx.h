@@ -25,6 +25,10 @@
 //                    wc_forward_levels_tol_host
 //   wc_coarsehost.cpp host side of the reduced-resolution inverse: wc_coarse_units,
 //                    the argument checks and wc_inverse_coarse_host
+//   wc_regionrule.cpp / wc_regionhost.cpp  the sub-box inverse: wc_region_align
+//                    and wc_region_units (plain C++, linked alone with
+//                    wc_regionmap.h by tests/cpp/test_regionrule.cpp), the
+//                    argument checks and wc_inverse_region_host
 #pragma once
 
 #include "wavelet_amd.h"
@@ -98,6 +102,11 @@ hipError_t launch_decode_corner(hipStream_t, const CornerDesc*, const FTile* dti
                                 unsigned long long* status, float* corner, uint32_t* err, int ordered, uint32_t* bad);
 hipError_t launch_corner_box(hipStream_t, const CornerDesc*, const FTile* ftiles, uint32_t nft, const float* corner,
                              float* out, const uint32_t* bad);
+// wc_region.hip: the region decode (over a prefix of the full plan's decode
+// tiles) into the compact units of the sub-box inverse
+hipError_t launch_decode_region(hipStream_t, const RegionDesc*, const FTile* dtiles, uint32_t ndt,
+                                const uint8_t* payload, const uint64_t* offsets, uint32_t* ticket,
+                                unsigned long long* status, float* compact, uint32_t* err, int ordered, uint32_t* bad);
 
 struct DevBuf {
     void* p = nullptr;
@@ -275,6 +284,10 @@ std::vector<int> level_runs(const wc_ctx* c, const wc_unit* units, int n);
 int validate_coarse(wc_ctx* c, const wc_unit* units, int n, const int32_t* levels, const int32_t* reduce,
                     const wc_unit* out_units);
 uint64_t rows_magic(int32_t d);
+
+// wc_regionhost.cpp (reduce NULL = all 0)
+int validate_region(wc_ctx* c, const wc_unit* units, int n, const int32_t* levels, const int32_t* reduce,
+                    const wc_region* regions, const wc_unit* out_units);
 
 // Bracket one launch with events when profiling is on.
 struct StageTimer {

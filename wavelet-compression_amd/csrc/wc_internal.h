@@ -101,6 +101,29 @@ struct CornerDesc {
 };
 static_assert(sizeof(CornerDesc) == 72, "descriptor of 8-B members first");
 
+// One unit of the sub-box decode (wc_region.hip k_decode_region): the payload's
+// box, the primed unit (w, h, d) = (W, H, D) >> r with L' = L - r levels, and
+// the region's origin and extent in cells of that resolution (wc_regionmap.h).
+// Built per call.  The units with L' = 0 also get a CornerDesc (w, h, d = the
+// extent) for k_corner_box.
+struct RegionDesc {
+    uint64_t dst_off;      // element offset of the compact unit in the coefficient scratch (the derived unit's coef_off)
+    uint64_t out_off;      // the unit's first output cell
+    uint64_t dmagic;       // div_rows magic of D
+    uint64_t hmagic;       // div_rows magic of H
+    int32_t W, H, D;       // the payload's box
+    int32_t want;          // the header's ncoeff field: W*H*D, or -L for L >= 2
+    uint32_t w, h, d;      // the primed box
+    uint32_t L;            // L' = L - r
+    uint32_t ox, oy, oz;   // the region's origin >> r
+    uint32_t sx, sy, sz;   // the region's extent >> r: the compact unit
+    uint32_t end;          // region_end: no needed pair at or past this flat position; 0: the region has no cells
+    uint32_t dt_begin;     // the unit's first look-back granule
+    uint32_t direct;       // 1: L' = 0, the compact unit is the result (k_corner_box)
+    uint32_t pad;
+};
+static_assert(sizeof(RegionDesc) == 104, "descriptor of 8-B members first");
+
 // One unit of the multi-level RMSE-tolerance mode (wc_leveltol.hip).  Built per
 // call: the levels and tolerances are not part of a plan.
 struct LtUnit {
