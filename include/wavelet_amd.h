@@ -467,6 +467,76 @@ int wc_forward_levels_tol_host(wc_ctx* ctx, const void* cells, int dtype, const 
                                const int32_t* levels, const double* tol, uint8_t* payload, uint64_t payload_capacity,
                                uint64_t* offsets, uint32_t* kept, float* thresh, double* bound, double* rmse);
 
+/* Opt-in size budget on the multi-level transform (NOT the reference's rule):
+ * each unit keeps its max_pairs largest weighted coefficients and never more,
+ * so its payload is at most 20 + 8 * max_pairs bytes (a pair is one kept
+ * coefficient: a byte budget is a pair budget).  The selection is exact, by a
+ * three-digit radix select on a 32-bit integer key.
+ *
+ * Setting, as for wc_forward_levels_tol.  A unit W x H x D with cells and L
+ * levels, 1 <= L <= WC_MAX_LEVELS; 2^L divides W, H and D (for L = 1: even
+ * dimensions).  A is the final flat array of wc_forward_levels, N = W*H*D;
+ * lvl(I, J, K) as defined above.  The caller gives max_pairs[u] = K, a uint32.
+ *
+ * Candidates.  For a coefficient c, m = the fp32 bits of |c| (bits &
+ * 0x7FFFFFFF).  c is a candidate iff 1 <= m <= 0x7F800000: +-0 and NaN are
+ * never kept, +-inf is a candidate.
+ * Key.  key(c) = m + ((WC_LTOL_SHIFT * (lvl - 1)) << WC_HIST_SHIFT): the
+ * magnitude's bit pattern moved up by 24 bins (1.5 octaves, about sqrt(8)) per
+ * level, the weighting wc_forward_levels_tol uses between levels.  The largest
+ * key is 0x7F800000 + (72 << 19) = 0x81C00000.
+ * Selection.  With at most K candidates T = 0.  Otherwise T = the (K + 1)-th
+ * largest key, counted with multiplicity.  Kept = the candidates with key > T:
+ * kept <= K always, and with more than K candidates kept + #{key == T} >=
+ * K + 1.  Candidates whose key EQUALS T (the same magnitude bits at the same
+ * level, or a coincidence across levels) are ALL dropped: there is no
+ * positional tie-break, so a unit with ties at the boundary keeps fewer than K
+ * (a constant box with a budget below its candidate count keeps nothing).
+ * Per-level thresholds.  d = T - ((WC_LTOL_SHIFT * (l - 1)) << WC_HIST_SHIFT)
+ * as a signed 64-bit value; thresh_l = the float with bits 0 if d <= 0,
+ * 0x7F800000 (+inf) if d >= 0x7F800000, d otherwise.  "|c| > thresh_l"
+ * (strict, false for NaN) is then exactly "candidate and key > T".
+ * Only integers enter: the host, the device and every run give the same bits.
+ *
+ * Payload.  The pairs of exactly those coefficients, in flat order, with the
+ * header of wc_forward_levels (ncoeff = -L for L >= 2); 20 + 8 * kept bytes.
+ * Slots, offsets and wc_payload_bound as in wc_forward_levels.  K >= the
+ * candidate count gives the bytes of wc_forward_levels with the explicit
+ * threshold 0.0f.  The decoders need no change.  A unit without cells keeps
+ * nothing.
+ *
+ *   wc_budget_thresholds: host-only; T -> thresh_1..levels.
+ *   wc_budget_select: host-only; the rule on one unit's final flat array
+ *     (nx * ny * nz floats, x slowest).  key receives T; thresh (levels floats)
+ *     and kept (#{key > T}) are nullable.
+ *   wc_forward_levels_budget: wc_forward_levels with per-unit pair budgets in
+ *     place of keep / thresh.  levels (n int32, NULL = all 1) and max_pairs (n
+ *     uint32): HOST, consumed before the call returns.  d_thresh (n x
+ *     WC_MAX_LEVELS floats, entries past levels[u] written 0.0f) and d_key (n
+ *     uint32, unit u's T): device, nullable.  Asynchronous on the context's
+ *     stream; nothing is read back between its passes.  It leaves nothing
+ *     staged.
+ *   wc_forward_levels_budget_host: host buffers; payloads packed as
+ *     wc_forward_host; thresh (n x WC_MAX_LEVELS), key, rmse (n each): host,
+ *     nullable; rmse = the ACTUAL RMSE of each unit's round trip, taken on the
+ *     device (wc_inverse_levels + wc_rmse).  The unit runs (WC_OPT_HOST_CHUNK)
+ *     go one after another.
+ * A level outside 1..WC_MAX_LEVELS, a dimension that 2^L does not divide on a
+ * unit with cells (for L = 1: an odd dimension) or a null required buffer:
+ * WC_ERR_INVALID naming the unit, before anything is launched; outputs stay
+ * untouched. */
+int wc_budget_thresholds(uint32_t key, int levels, float* thresh);
+int wc_budget_select(const float* flat, int32_t nx, int32_t ny, int32_t nz, int levels, uint32_t max_pairs,
+                     uint32_t* key, float* thresh, uint32_t* kept);
+int wc_forward_levels_budget(wc_ctx* ctx, const void* d_cells, int dtype, const wc_unit* units, int n,
+                             const int32_t* levels, const uint32_t* max_pairs, uint8_t* d_payload,
+                             uint64_t payload_capacity, uint64_t* d_offsets, uint32_t* d_kept, float* d_thresh,
+                             uint32_t* d_key);
+int wc_forward_levels_budget_host(wc_ctx* ctx, const void* cells, int dtype, const wc_unit* units, int n,
+                                  const int32_t* levels, const uint32_t* max_pairs, uint8_t* payload,
+                                  uint64_t payload_capacity, uint64_t* offsets, uint32_t* kept, float* thresh,
+                                  uint32_t* key, double* rmse);
+
 /* Opt-in reduced-resolution decode (not in the reference): the box at 1/2^r
  * resolution straight from a payload, without the work of the full resolution.
  * The low-pass corner of the coefficient array after undoing levels L..r+1 is
@@ -698,7 +768,8 @@ int wc_decompose_host(wc_ctx* ctx, const void* cells, int dtype, const wc_unit* 
                                  units' bins are counted inside the transform stage) */
 #define WC_STAGE_PAIRS 6      /* header check + pair counts of wc_inverse_rows with a caller row index */
 #define WC_STAGE_TOL 7        /* per-unit bins + threshold pick of the RMSE-tolerance mode (wc_forward_tol); per-level bins, pick
-                                 and mask pass of wc_forward_levels_tol */
+                                 and mask pass of wc_forward_levels_tol; radix select and mask pass of
+                                 wc_forward_levels_budget */
 #define WC_STAGE_LEVELS 8    /* level passes, key pass and header patch of the multi-level mode (wc_forward_levels,
                                  wc_inverse_levels) */
 #define WC_NUM_STAGES 9

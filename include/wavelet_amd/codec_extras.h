@@ -59,4 +59,16 @@ Box3D decompress_region(const std::string& file_path, std::array<int, 3> lo, std
 std::vector<CompressedWavelet> compress_rmse(multiBox3D& box, std::vector<int> components, int levels, double rmse,
                                              int time, int level, int box_index, std::string compressed_dir);
 
+// compress() under a size budget in place of keep (GPU, wc_forward_levels_budget_host;
+// not in the reference): every component of N cells is transformed with the levels
+// its dimensions admit, at most `levels`, and keeps its (max(20, floor(4 N / ratio)) -
+// 20) / 8 largest weighted coefficients and never more, so that its serialized
+// payload (before xz) is at most 1 / ratio of its 4 N bytes, or the 20-byte header.
+// Coefficients that tie at the boundary are all dropped.  Writes the usual per-box
+// .xz files, which decompress(), decompress_coarse() and decompress_region() read as
+// they are, and returns the structs.  A component with cells and an odd dimension
+// exits with the library's message, as the other errors do.
+std::vector<CompressedWavelet> compress_budget(multiBox3D& box, std::vector<int> components, int levels, double ratio,
+                                               int time, int level, int box_index, std::string compressed_dir);
+
 }  // namespace wavelet_amd

@@ -36,6 +36,7 @@ EXPORTED = (
     "wc_coarse_units", "wc_inverse_coarse", "wc_inverse_coarse_host",
     "wc_tol_levels_threshold", "wc_forward_levels_tol", "wc_forward_levels_tol_host",
     "wc_region_align", "wc_region_units", "wc_inverse_region", "wc_inverse_region_host",
+    "wc_budget_thresholds", "wc_budget_select", "wc_forward_levels_budget", "wc_forward_levels_budget_host",
 )
 WC_MAX_LEVELS = 4  # levels of the opt-in multi-level transform (1 = the reference's codec)
 WC_LTOL_SHIFT = 24  # bins between the walks of two adjacent levels in the multi-level RMSE-tolerance rule
@@ -151,6 +152,12 @@ def load_library() -> ctypes.CDLL:
                                           ctypes.POINTER(ctypes.c_double)]),
         "wc_forward_levels_tol": (i32, [vp, vp, i32, up, i32, vp, vp, vp, u64, vp, vp, vp, vp]),
         "wc_forward_levels_tol_host": (i32, [vp, vp, i32, up, i32, vp, vp, vp, u64, vp, vp, vp, vp, vp]),
+        "wc_budget_thresholds": (i32, [ctypes.c_uint32, i32, ctypes.POINTER(ctypes.c_float)]),
+        "wc_budget_select": (i32, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, i32, ctypes.c_uint32,
+                                   ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_float),
+                                   ctypes.POINTER(ctypes.c_uint32)]),
+        "wc_forward_levels_budget": (i32, [vp, vp, i32, up, i32, vp, vp, vp, u64, vp, vp, vp, vp]),
+        "wc_forward_levels_budget_host": (i32, [vp, vp, i32, up, i32, vp, vp, vp, u64, vp, vp, vp, vp, vp]),
         "wc_region_align": (i32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, i32, rp, rp]),
         "wc_region_units": (i32, [up, rp, vp, i32, up, ctypes.POINTER(u64)]),
         "wc_inverse_region": (i32, [vp, vp, vp, up, i32, vp, vp, rp, up, vp]),
@@ -354,6 +361,22 @@ class Context:
                                                   ctypes.c_void_p(d_offsets), ctypes.c_void_p(d_kept),
                                                   ctypes.c_void_p(d_thresh or 0), ctypes.c_void_p(d_bound or 0)))
 
+    def forward_levels_budget(self, d_cells: int, dtype: int, units, n: int, levels, max_pairs, d_payload: int,
+                              capacity: int, d_offsets: int, d_kept: int, d_thresh: int | None = None,
+                              d_key: int | None = None):
+        """wc_forward_levels with per-unit pair budgets (n host uint32, or one value
+        for all) in place of keep / thresh: each unit keeps its max_pairs largest
+        weighted coefficients and never more.  levels None: all 1.  d_thresh (n x
+        WC_MAX_LEVELS floats) / d_key (n uint32, the units' T): optional device
+        outputs."""
+        lv = None if levels is None else _levels_array(levels, n)
+        k = _pairs_array(max_pairs, n)
+        self._check(self._L.wc_forward_levels_budget(self._h, ctypes.c_void_p(d_cells), dtype, units, n,
+                                                     None if lv is None else lv.ctypes.data, k.ctypes.data,
+                                                     ctypes.c_void_p(d_payload), capacity, ctypes.c_void_p(d_offsets),
+                                                     ctypes.c_void_p(d_kept), ctypes.c_void_p(d_thresh or 0),
+                                                     ctypes.c_void_p(d_key or 0)))
+
     def decompose_levels(self, d_cells: int, dtype: int, units, n: int, levels, d_flat: int):
         lv = _levels_array(levels, n)
         self._check(self._L.wc_decompose_levels(self._h, ctypes.c_void_p(d_cells), dtype, units, n, lv.ctypes.data,
@@ -504,6 +527,30 @@ class Context:
                                                        rmse.ctypes.data if want_rmse else None))
         return payload, offsets, kept[:n], thresh[:n], bound[:n], rmse[:n] if want_rmse else None
 
+    def forward_levels_budget_host(self, cells: np.ndarray, units, n: int, levels, max_pairs, want_rmse: bool = True):
+        """wc_forward_levels_budget_host -> (payload, offsets, kept, thresh [n,
+        WC_MAX_LEVELS], key, rmse); rmse is the actual RMSE of each unit's round
+        trip, taken on the device (None, and no round trip, without want_rmse)."""
+        c = np.ascontiguousarray(cells)
+        if c.dtype not in (np.float32, np.float64):
+            raise TypeError("cells must be float32 or float64")
+        dtype = WC_F64 if c.dtype == np.float64 else WC_F32
+        lv = None if levels is None else _levels_array(levels, n)
+        k = _pairs_array(max_pairs, n)
+        cap = payload_bound(units, n)
+        payload = np.empty(cap, np.uint8)
+        offsets = np.zeros(n + 1, np.uint64)
+        kept = np.zeros(max(n, 1), np.uint32)
+        thresh = np.zeros((max(n, 1), WC_MAX_LEVELS), np.float32)
+        key = np.zeros(max(n, 1), np.uint32)
+        rmse = np.zeros(max(n, 1), np.float64) if want_rmse else None
+        self._check(self._L.wc_forward_levels_budget_host(self._h, c.ctypes.data, dtype, units, n,
+                                                          None if lv is None else lv.ctypes.data, k.ctypes.data,
+                                                          payload.ctypes.data, cap, offsets.ctypes.data,
+                                                          kept.ctypes.data, thresh.ctypes.data, key.ctypes.data,
+                                                          rmse.ctypes.data if want_rmse else None))
+        return payload, offsets, kept[:n], thresh[:n], key[:n], rmse[:n] if want_rmse else None
+
     def forward_levels_host(self, cells: np.ndarray, units, n: int, levels, keep: float,
                             thresh: float | None = None):
         """wc_forward_levels_host -> (payload, offsets, kept), packed as forward_host."""
@@ -651,6 +698,17 @@ def _tol_array(tol, n: int) -> np.ndarray:
     return t
 
 
+def _pairs_array(max_pairs, n: int) -> np.ndarray:
+    """Per-unit pair budgets as n contiguous uint32 (one value: the same for every unit)."""
+    k = np.asarray(max_pairs)
+    if k.size and (k.min() < 0 or k.max() > 0xFFFFFFFF):
+        raise ValueError("max_pairs: values in 0..2^32 - 1")
+    k = np.ascontiguousarray(np.broadcast_to(k, (n,)) if k.ndim == 0 else k, dtype=np.uint32)
+    if k.shape != (n,):
+        raise ValueError(f"max_pairs: one value or {n} values")
+    return k
+
+
 def _levels_array(levels, n: int) -> np.ndarray:
     """Per-unit levels as n contiguous int32 (one value: the same for every unit)."""
     lv = np.ascontiguousarray(np.broadcast_to(np.asarray(levels, np.int32), (n,)) if np.ndim(levels) == 0 else levels,
@@ -752,6 +810,32 @@ def tol_levels_threshold(counts: np.ndarray, levels: int, ncoeff: int, tol: floa
     if rc:
         raise WaveletError(rc, "wc_tol_levels_threshold: invalid argument")
     return [float(t[l]) for l in range(L)], float(b.value)
+
+
+def budget_thresholds(key: int, levels: int):
+    """wc_budget_thresholds (host only): the fp32 thresholds of levels 1..L that
+    keep exactly the candidates whose key is above `key`."""
+    t = (ctypes.c_float * WC_MAX_LEVELS)()
+    rc = load_library().wc_budget_thresholds(int(key), int(levels), t)
+    if rc:
+        raise WaveletError(rc, "wc_budget_thresholds: invalid argument")
+    return [float(t[l]) for l in range(int(levels))]
+
+
+def budget_select(flat: np.ndarray, dims, levels: int, max_pairs: int):
+    """wc_budget_select (host only): (T, fp32 thresholds of levels 1..L, kept) of
+    the size-budget rule on one unit's final flat array, dims = (W, H, D)."""
+    f = np.ascontiguousarray(flat, dtype=np.float32).ravel()
+    W, H, D = (int(v) for v in dims)
+    if W >= 0 and H >= 0 and D >= 0 and f.size != W * H * D:
+        raise ValueError("flat must have W * H * D values")
+    t = (ctypes.c_float * WC_MAX_LEVELS)()
+    key, kept = ctypes.c_uint32(), ctypes.c_uint32()
+    rc = load_library().wc_budget_select(f.ctypes.data, W, H, D, int(levels), int(max_pairs), ctypes.byref(key), t,
+                                         ctypes.byref(kept))
+    if rc:
+        raise WaveletError(rc, "wc_budget_select: invalid argument")
+    return int(key.value), [float(t[l]) for l in range(int(levels))], int(kept.value)
 
 
 def unit_payload(payload: np.ndarray, offsets: np.ndarray, kept: np.ndarray, u: int) -> bytes:

@@ -120,7 +120,8 @@ def _pairs_need32(vals: np.ndarray) -> bool:
     return bool(vals.size and np.any(np.abs(vals.astype(np.float64)) > 32767))
 
 
-def compress_payloads(boxes: Sequence[np.ndarray], keep: float, device: int = 0, levels: int = 1, rmse=None):
+def compress_payloads(boxes: Sequence[np.ndarray], keep: float, device: int = 0, levels: int = 1, rmse=None,
+                      max_bytes=None, ratio=None):
     """Batched forward path: list of Box3D -> list of serialized payload bytes.
 
     One wc_forward_host_units call for the whole list (all units in one launch
@@ -131,18 +132,40 @@ def compress_payloads(boxes: Sequence[np.ndarray], keep: float, device: int = 0,
     rmse (not a reference parameter; None: the keep rule): the tolerated RMSE of
     every box, one value or one per box, in place of keep, with one threshold
     per level (wc_forward_levels_tol_host); boxes with cells need even
-    dimensions.  The payload format is the same."""
+    dimensions.  max_bytes (not a reference parameter; an int or one per box):
+    every payload is at most max_bytes long: the box keeps its (max_bytes - 20)
+    // 8 largest weighted coefficients (wc_forward_levels_budget_host; ties at
+    the boundary are all dropped).  ratio: max_bytes = max(20, floor(4 * N /
+    ratio)) per box of N cells.  rmse, max_bytes and ratio exclude each other.
+    The payload format is the same."""
+    if sum(v is not None for v in (rmse, max_bytes, ratio)) > 1:
+        raise ValueError("rmse, max_bytes and ratio are mutually exclusive")
     dims = [_box_dims(b) for b in boxes]
+    budget = None
+    if ratio is not None:
+        if not float(ratio) > 0:
+            raise ValueError(f"ratio: a positive number, not {ratio!r}")
+        budget = [max(20, int(4 * W * H * D / float(ratio))) for W, H, D in dims]
+    elif max_bytes is not None:
+        budget = [int(max_bytes)] * len(dims) if np.ndim(max_bytes) == 0 else [int(v) for v in max_bytes]
+        if len(budget) != len(dims):
+            raise ValueError(f"max_bytes: one value or {len(dims)} values")
+        if any(v < 20 for v in budget):
+            raise ValueError("max_bytes: a payload's header alone takes 20 bytes")
     arrs = [np.ascontiguousarray(b, np.float32) for b in boxes]
     if not 1 <= int(levels) <= capi.WC_MAX_LEVELS:
         raise ValueError(f"levels: 1..{capi.WC_MAX_LEVELS}, not {levels!r}")
-    if levels > 1 or rmse is not None:
+    if levels > 1 or rmse is not None or budget is not None:
         units, n, extent = capi.make_units(dims)
         cells = np.zeros(max(extent, 1), np.float32)
         for i, a in enumerate(arrs):
             cells[units[i].cell_offset:units[i].cell_offset + a.size] = a.ravel()
         lv = [capi.levels_for(*d, levels) for d in dims]
-        if rmse is not None:
+        if budget is not None:
+            pairs = [min((v - 20) // 8, 0xFFFFFFFF) for v in budget]
+            payload, offsets, kept = context(device).forward_levels_budget_host(cells, units, n, lv, pairs,
+                                                                                want_rmse=False)[:3]
+        elif rmse is not None:
             payload, offsets, kept = context(device).forward_levels_tol_host(cells, units, n, lv, rmse, want_rmse=False)[:3]
         else:
             payload, offsets, kept = context(device).forward_levels_host(cells, units, n, lv, keep)

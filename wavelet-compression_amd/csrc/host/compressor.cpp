@@ -187,3 +187,41 @@ std::vector<CompressedWavelet> wavelet_amd::compress_rmse(multiBox3D& box, std::
           "GPU forward");
     return write_components(payload.get(), offsets, kept, components, time, level, box_index, compressed_dir);
 }
+
+std::vector<CompressedWavelet> wavelet_amd::compress_budget(multiBox3D& box, std::vector<int> components, int levels,
+                                                            double ratio, int time, int level, int box_index,
+                                                            std::string compressed_dir) {
+    const int n = static_cast<int>(components.size());
+    if (n == 0) return {};
+    if (levels < 1 || levels > WC_MAX_LEVELS)
+        fatal("compress_budget: levels " + std::to_string(levels) + " outside 1.." + std::to_string(WC_MAX_LEVELS));
+    if (!(ratio > 0.0)) fatal("compress_budget: the ratio must be positive");
+    // the host form takes one cell buffer: the components back to back, each start 4-element aligned
+    std::vector<wc_unit> units(n);
+    std::vector<int32_t> lv(n);
+    std::vector<uint32_t> pairs(n);
+    uint64_t extent = 0;
+    for (int c = 0; c < n; ++c) {
+        const Box3D& b = box.at(c);
+        extent = (extent + 3) / 4 * 4;
+        units[c] = wc_unit{extent, (int32_t)b.width(), (int32_t)b.height(), (int32_t)b.depth(), 0};
+        lv[c] = wc_levels_for(units[c].nx, units[c].ny, units[c].nz, levels);
+        // a payload of at most max(20, floor(4 N / ratio)) bytes: 20 of header, 8 per pair
+        const double bytes = std::max(20.0, std::floor(4.0 * (double)b.data_size() / ratio));
+        pairs[c] = (uint32_t)std::min((bytes - 20.0) / 8.0, 4294967295.0);
+        extent += b.data_size();
+    }
+    std::vector<float> cells(extent);
+    for (int c = 0; c < n; ++c)
+        if (box.at(c).data_size())
+            std::memcpy(cells.data() + units[c].cell_offset, box.at(c).data(), sizeof(float) * box.at(c).data_size());
+    const uint64_t cap = wc_payload_bound(units.data(), n);
+    std::unique_ptr<uint8_t[]> payload(new uint8_t[cap]);
+    std::vector<uint64_t> offsets(n + 1);
+    std::vector<uint32_t> kept(n);
+    wc_ctx* ctx = thread_ctx();
+    check(ctx, wc_forward_levels_budget_host(ctx, cells.data(), WC_F32, units.data(), n, lv.data(), pairs.data(),
+                                             payload.get(), cap, offsets.data(), kept.data(), nullptr, nullptr, nullptr),
+          "GPU forward");
+    return write_components(payload.get(), offsets, kept, components, time, level, box_index, compressed_dir);
+}

@@ -1,0 +1,356 @@
+// wc_budget.hip — the size-budget mode of the opt-in multi-level transform
+// (wc_forward_levels_budget in include/wavelet_amd.h): per unit, the threshold T
+// that keeps the max_pairs largest weighted coefficients and never more, by a
+// three-digit radix select on the 32-bit key
+//   key(c) = bits of |c| + ((WC_LTOL_SHIFT * (lvl - 1)) << WC_HIST_SHIFT)
+// over the candidates (1 <= bits of |c| <= 0x7F800000: +-0 and NaN are none).
+//
+// Not part of the reference's codec.  Three passes over the staged final array,
+// each HBM-bound at 4 B per coefficient, with the level of a position, the LDS
+// bins and the tile pipeline of wc_leveltol.h:
+//   digit 1  key >> 19        per-level bins of the magnitude (as k_ltol_solo,
+//                             zeros not counted); the walk goes down over
+//                             total[s] = sum_l cnt[l][s - 24 (l - 1)]
+//   digit 2  (key >> 7) & 0xFFF  only keys whose first digit is the boundary s*
+//   digit 3  key & 0x7F          only keys with key >> 7 == (s*, second digit)
+// A walk over a digit's counts, downward from the largest value, finds d* with
+//   above + #(d > d*) <= K < above + #(d >= d*)
+// and adds #(d > d*) to `above`; after the third digit T = the (K + 1)-th
+// largest key and above = #(key > T) <= K.  A unit with at most K candidates is
+// done after the first digit with T = 0.  Only integer counts enter.
+//   k_budget_solo<NL>   one workgroup per unit of up to WC_OPT_TOL_SOLO_TILES
+//                       flat tiles: the three digits in one launch (the second
+//                       and third read find the unit in the caches), then
+//                       thresh[u][1..L] / key[u]
+//   k_budget_split<NL>  larger units, a run of tiles per workgroup: digit 1's LDS
+//                       bins, the nonzero ones added to the unit's NL x 16 KiB
+//                       global bins
+//   k_budget_digit<P>   the same tile runs for digit P = 2, 3: one 16 KiB bin
+//                       set (few keys pass the filter, so few atomics); leaves
+//                       at once when the unit's state says done
+//   k_budget_pick<P>    one wave per split unit (a later launch): the walk over
+//                       the unit's global bins, its state {prefix, above, done}
+//                       and, at the end, thresh / key
+// The mask pass and the emit are wc_leveltol.hip's and wc_emit.hip's, unchanged.
+// LDS per workgroup as k_ltol_solo: (NL + 1) x 16 KiB.
+#include "wc_leveltol.h"
+
+namespace wc {
+
+constexpr uint32_t kBgInf = 0x7f800000u;
+constexpr uint32_t kBgLevelStep = (uint32_t)WC_LTOL_SHIFT << kHistShift;  // a level's offset in the key
+constexpr int kBgMidBins = 4096, kBgLowBins = 128;
+static_assert(kBgMidBins == kHistBins && kHistShift == 19, "digits of 12 + 12 + 7 bits over a 16 KiB bin set");
+
+// magnitude bits m of a candidate at level index lv (level - 1)
+__device__ __forceinline__ bool bg_candidate(uint32_t m) { return m - 1u < kBgInf; }  // 1 <= m <= 0x7F800000
+__device__ __forceinline__ uint32_t bg_key(uint32_t m, uint32_t lv) { return m + lv * kBgLevelStep; }
+
+// Tiles [t0, t1) of unit U, f(m, lv) on every coefficient; the loads of tile
+// t + 1 are issued before tile t is visited (lt_bin_tiles).
+template <class F>
+__device__ __forceinline__ void bg_tiles(const float* __restrict__ coef, const UnitDev& U, const LtGeom& G,
+                                         uint32_t t0, uint32_t t1, F f) {
+    if (t0 >= t1) return;
+    float4 cur[kLtIt], nxt[kLtIt];
+    uint32_t len = lt_load(cur, coef, U, t0), nlen = 0;
+    for (uint32_t t = t0; t < t1; ++t) {
+        const bool more = t + 1 < t1;  // uniform
+        if (more) nlen = lt_load(nxt, coef, U, t + 1);
+#pragma unroll
+        for (int it = 0; it < kLtIt; ++it) {
+            const uint32_t e = 4 * (it * kLtThreads + threadIdx.x);
+            if (e >= len) continue;  // len % 4 == 0: the load is inside the unit or outside it
+            const uint32_t lv = lt_levels4(G, t * (uint32_t)kFlatTile + e);
+            f(__float_as_uint(cur[it].x) & 0x7fffffffu, lv & 3u);
+            f(__float_as_uint(cur[it].y) & 0x7fffffffu, (lv >> 2) & 3u);
+            f(__float_as_uint(cur[it].z) & 0x7fffffffu, (lv >> 4) & 3u);
+            f(__float_as_uint(cur[it].w) & 0x7fffffffu, lv >> 6);
+        }
+        if (more) {
+#pragma unroll
+            for (int it = 0; it < kLtIt; ++it) cur[it] = nxt[it];
+            len = nlen;
+        }
+    }
+}
+
+// digit 1 into the per-level LDS bins (lt_add1 without the zeros)
+__device__ __forceinline__ void bg_bin_top(uint32_t* h, const float* __restrict__ coef, const UnitDev& U,
+                                           const LtGeom& G, uint32_t t0, uint32_t t1) {
+    const uint32_t set = threadIdx.x & 1u;
+    bg_tiles(coef, U, G, t0, t1, [&](uint32_t m, uint32_t lv) {
+        if (!bg_candidate(m)) return;
+        const uint32_t b = m >> kHistShift;
+        const uint32_t i = lv ? (lv + 1u) * kHistBins + b : set ? kHistBins + ((b + kLtRot) & (kHistBins - 1)) : b;
+        atomicAdd(h + i, 1u);
+    });
+}
+// digit 2 of the keys with first digit s
+__device__ __forceinline__ void bg_bin_mid(uint32_t* h, const float* __restrict__ coef, const UnitDev& U,
+                                           const LtGeom& G, uint32_t t0, uint32_t t1, uint32_t s) {
+    bg_tiles(coef, U, G, t0, t1, [&](uint32_t m, uint32_t lv) {
+        const uint32_t k = bg_key(m, lv);
+        if (bg_candidate(m) && (k >> kHistShift) == s) atomicAdd(h + ((k >> 7) & (kBgMidBins - 1)), 1u);
+    });
+}
+// digit 3 of the keys with key >> 7 == prefix
+__device__ __forceinline__ void bg_bin_low(uint32_t* h, const float* __restrict__ coef, const UnitDev& U,
+                                           const LtGeom& G, uint32_t t0, uint32_t t1, uint32_t prefix) {
+    bg_tiles(coef, U, G, t0, t1, [&](uint32_t m, uint32_t lv) {
+        const uint32_t k = bg_key(m, lv);
+        if (bg_candidate(m) && (k >> 7) == prefix) atomicAdd(h + (k & (kBgLowBins - 1)), 1u);
+    });
+}
+
+// The walk by one full wave (lane ln) over cnt(d), d = nbins - 1 down to 0, 64
+// values per round (lane 0 the largest): true with d* and above += #(d > d*)
+// when above + #(d >= d*) > K for some d, else false with above += every count.
+// Counts and above stay below 2^31 (N < 2^31).
+template <class F>
+__device__ __forceinline__ bool bg_walk(F cnt, int nbins, uint32_t K, int ln, uint32_t& above, int& dstar) {
+    for (int top = nbins - 1; top >= 0; top -= kWave) {
+        const int d = top - ln;
+        const uint32_t c = d >= 0 ? cnt(d) : 0u;
+        uint32_t incl = c;
+#pragma unroll
+        for (int o = 1; o < kWave; o <<= 1) {
+            const uint32_t t = __shfl_up(incl, o, kWave);
+            if (ln >= o) incl += t;
+        }
+        const unsigned long long over = __ballot(above + incl > K);
+        if (over) {  // uniform
+            const int j = __ffsll((long long)over) - 1;
+            above += __shfl(incl - c, j, kWave);
+            dstar = top - j;
+            return true;
+        }
+        above += __shfl(incl, kWave - 1, kWave);
+    }
+    return false;
+}
+
+// digit 1's count of s over the levels: level 1's bins at h, level l >= 2's at
+// h + off2 + (l - 2) * kHistBins (lt_pick's layout)
+__device__ __forceinline__ uint32_t bg_top_count(const uint32_t* h, int off2, int L, int s) {
+    uint32_t c = 0u;
+#pragma unroll
+    for (int l = 0; l < WC_MAX_LEVELS; ++l) {
+        const int b = s - WC_LTOL_SHIFT * l;
+        if (l < L && b >= 0 && b < kHistBins) c += h[(l ? off2 + (l - 1) * kHistBins : 0) + b];
+    }
+    return c;
+}
+__device__ __forceinline__ int bg_top_bins(int L) { return kHistBins + WC_LTOL_SHIFT * (L - 1); }
+
+// thresh_l of T (include/wavelet_amd.h, wc_budget_thresholds); entries past L are 0.0f
+__device__ __forceinline__ void bg_write(uint32_t T, int L, float* __restrict__ thresh, uint32_t* __restrict__ key) {
+#pragma unroll
+    for (int l = 0; l < WC_MAX_LEVELS; ++l) {
+        const long long d = (long long)T - (long long)((uint32_t)l * kBgLevelStep);
+        thresh[l] = l >= L || d <= 0 ? 0.0f : d >= (long long)kBgInf ? __uint_as_float(kBgInf) : __uint_as_float((uint32_t)d);
+    }
+    if (key) *key = T;
+}
+
+// Workgroup u owns unit u unless the unit is split (lt[u].slot != kLtSolo).
+template <int NL>
+__global__ __launch_bounds__(kLtThreads) void k_budget_solo(const UnitDev* __restrict__ units,
+                                                          const LtUnit* __restrict__ lt,
+                                                          const uint32_t* __restrict__ max_pairs,
+                                                          const float* __restrict__ coef, float* __restrict__ thresh,
+                                                          uint32_t* __restrict__ key) {
+    const uint32_t u = blockIdx.x;
+    const LtUnit T = lt[u];
+    if (T.slot != kLtSolo) return;  // uniform
+    __shared__ uint32_t h[(NL + 1) * kHistBins];
+    // found, digit, above: in level 1's second bin set, free once lt_fold has summed it into the first
+    // (a word more of LDS than k_ltol_solo's would cost a workgroup per CU at NL = 1 and NL = 4)
+    uint32_t* st = h + kHistBins;
+    const UnitDev& U = units[u];
+    const LtGeom G = lt_geom(U, T);
+    const uint32_t K = max_pairs[u], nt = U.nftiles;
+    const int L = (int)T.levels, ln = (int)threadIdx.x;
+    float* th = thresh + (size_t)u * WC_MAX_LEVELS;
+    uint32_t* ky = key ? key + u : nullptr;
+
+    lt_zero(h, (NL + 1) * kHistBins);
+    bg_bin_top(h, coef, U, G, 0u, nt);
+    lt_fold(h);
+    if (ln < kWave) {
+        uint32_t above = 0u;
+        int d = 0;
+        const bool found = bg_walk([&](int s) { return bg_top_count(h, 2 * kHistBins, L, s); }, bg_top_bins(L), K, ln,
+                                   above, d);
+        if (ln == 0) {
+            st[0] = found ? 1u : 0u;
+            st[1] = (uint32_t)d;
+            st[2] = above;
+        }
+    }
+    __syncthreads();
+    if (!st[0]) {  // uniform: at most K candidates
+        if (ln == 0) bg_write(0u, L, th, ky);
+        return;
+    }
+    const uint32_t s = st[1];
+    lt_zero(h, kBgMidBins);  // (its barrier: st has been read)
+    bg_bin_mid(h, coef, U, G, 0u, nt, s);
+    __syncthreads();
+    if (ln < kWave) {
+        uint32_t above = st[2];
+        int d = 0;
+        (void)bg_walk([&](int i) { return h[i]; }, kBgMidBins, K, ln, above, d);
+        if (ln == 0) {
+            st[1] = (s << 12) | (uint32_t)d;
+            st[2] = above;
+        }
+    }
+    __syncthreads();
+    const uint32_t prefix = st[1];
+    lt_zero(h, kBgLowBins);
+    bg_bin_low(h, coef, U, G, 0u, nt, prefix);
+    __syncthreads();
+    if (ln < kWave) {
+        uint32_t above = st[2];
+        int d = 0;
+        (void)bg_walk([&](int i) { return h[i]; }, kBgLowBins, K, ln, above, d);
+        if (ln == 0) bg_write((prefix << 7) | (uint32_t)d, L, th, ky);
+    }
+}
+
+// Work item i: tiles [items[i].y, + chunk) of split unit items[i].x, digit 1's
+// bins added to the unit's global bins gbins + slot * NL * kHistBins
+// (level-major, zeroed by the caller).
+template <int NL>
+__global__ __launch_bounds__(kLtThreads) void k_budget_split(const UnitDev* __restrict__ units,
+                                                           const LtUnit* __restrict__ lt,
+                                                           const uint2* __restrict__ items, uint32_t chunk,
+                                                           const float* __restrict__ coef,
+                                                           uint32_t* __restrict__ gbins) {
+    __shared__ uint32_t h[(NL + 1) * kHistBins];
+    lt_zero(h, (NL + 1) * kHistBins);
+    const uint2 it = items[blockIdx.x];
+    const UnitDev& U = units[it.x];
+    const LtUnit T = lt[it.x];
+    bg_bin_top(h, coef, U, lt_geom(U, T), it.y, min(it.y + chunk, U.nftiles));
+    lt_fold(h);
+    uint32_t* __restrict__ g = gbins + (size_t)T.slot * NL * kHistBins;
+    for (int l = 1; l <= (int)T.levels; ++l) {
+        const uint32_t* hl = h + lt_base(l);
+        for (int i = threadIdx.x; i < kHistBins; i += kLtThreads)
+            if (hl[i]) atomicAdd(g + (l - 1) * kHistBins + i, hl[i]);
+    }
+}
+
+// The same work items for digit P (2 or 3) of the keys that share the unit's
+// prefix, added to the unit's one bin set gbins + slot * kHistBins (zeroed by
+// the caller).
+template <int P>
+__global__ __launch_bounds__(kLtThreads) void k_budget_digit(const UnitDev* __restrict__ units,
+                                                           const LtUnit* __restrict__ lt,
+                                                           const uint2* __restrict__ items, uint32_t chunk,
+                                                           const float* __restrict__ coef,
+                                                           const BudgetState* __restrict__ state,
+                                                           uint32_t* __restrict__ gbins) {
+    constexpr int kBins = P == 2 ? kBgMidBins : kBgLowBins;
+    const uint2 it = items[blockIdx.x];
+    const LtUnit T = lt[it.x];
+    const BudgetState S = state[T.slot];
+    if (S.done) return;  // uniform
+    __shared__ uint32_t h[kBins];
+    lt_zero(h, kBins);
+    const UnitDev& U = units[it.x];
+    const uint32_t t1 = min(it.y + chunk, U.nftiles);
+    if (P == 2)
+        bg_bin_mid(h, coef, U, lt_geom(U, T), it.y, t1, S.prefix);
+    else
+        bg_bin_low(h, coef, U, lt_geom(U, T), it.y, t1, S.prefix);
+    __syncthreads();
+    uint32_t* __restrict__ g = gbins + (size_t)T.slot * kHistBins;
+    for (int i = threadIdx.x; i < kBins; i += kLtThreads)
+        if (h[i]) atomicAdd(g + i, h[i]);
+}
+
+// Workgroup s (one wave): the walk of split unit split_units[s] over digit P's
+// global bins (P = 1: nl level sets per unit; P = 2, 3: one set per unit).
+template <int P>
+__global__ __launch_bounds__(kWave) void k_budget_pick(const LtUnit* __restrict__ lt,
+                                                     const uint32_t* __restrict__ split_units,
+                                                     const uint32_t* __restrict__ max_pairs,
+                                                     const uint32_t* __restrict__ gbins, int nl,
+                                                     BudgetState* __restrict__ state, float* __restrict__ thresh,
+                                                     uint32_t* __restrict__ key) {
+    const uint32_t u = split_units[blockIdx.x];
+    const int L = (int)lt[u].levels, ln = (int)threadIdx.x;
+    const uint32_t K = max_pairs[u];
+    float* th = thresh + (size_t)u * WC_MAX_LEVELS;
+    uint32_t* ky = key ? key + u : nullptr;
+    BudgetState S = state[blockIdx.x];
+    int d = 0;
+    if (P == 1) {
+        const uint32_t* h = gbins + (size_t)blockIdx.x * nl * kHistBins;
+        uint32_t above = 0u;
+        const bool found = bg_walk([&](int s) { return bg_top_count(h, kHistBins, L, s); }, bg_top_bins(L), K, ln, above, d);
+        if (ln == 0) {
+            state[blockIdx.x] = {(uint32_t)d, above, found ? 0u : 1u, 0u};
+            if (!found) bg_write(0u, L, th, ky);
+        }
+        return;
+    }
+    if (S.done) return;  // uniform
+    const uint32_t* h = gbins + (size_t)blockIdx.x * kHistBins;
+    (void)bg_walk([&](int i) { return h[i]; }, P == 2 ? kBgMidBins : kBgLowBins, K, ln, S.above, d);
+    if (ln != 0) return;
+    if (P == 2) {
+        state[blockIdx.x] = {(S.prefix << 12) | (uint32_t)d, S.above, 0u, 0u};
+    } else {
+        state[blockIdx.x] = {S.prefix, S.above, 1u, 0u};
+        bg_write((S.prefix << 7) | (uint32_t)d, L, th, ky);
+    }
+}
+
+// lt[n]: the units' descriptors (tol unused); max_pairs[n]; items[nitems]: the
+// split units' tile runs of `chunk` tiles; split_units[nsplit]; gbins: nsplit x
+// maxl x kHistBins; state[nsplit]; thresh: n x WC_MAX_LEVELS floats; key: n
+// uint32 or null.  Every grid follows from the plan: nothing is read back.
+hipError_t launch_budget(hipStream_t st, const UnitDev* units, int n, const LtUnit* lt, const uint32_t* max_pairs,
+                         const uint2* items, uint32_t nitems, uint32_t chunk, const uint32_t* split_units,
+                         uint32_t nsplit, int maxl, const float* coef, uint32_t* gbins, BudgetState* state,
+                         float* thresh, uint32_t* key) {
+    if (n <= 0) return hipSuccess;
+    hipError_t e = hipSuccess;
+    if ((uint32_t)n > nsplit) {
+        switch (maxl) {
+            case 1: k_budget_solo<1><<<(uint32_t)n, kLtThreads, 0, st>>>(units, lt, max_pairs, coef, thresh, key); break;
+            case 2: k_budget_solo<2><<<(uint32_t)n, kLtThreads, 0, st>>>(units, lt, max_pairs, coef, thresh, key); break;
+            case 3: k_budget_solo<3><<<(uint32_t)n, kLtThreads, 0, st>>>(units, lt, max_pairs, coef, thresh, key); break;
+            default: k_budget_solo<4><<<(uint32_t)n, kLtThreads, 0, st>>>(units, lt, max_pairs, coef, thresh, key); break;
+        }
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    if (!nsplit) return e;
+    const size_t set_bytes = sizeof(uint32_t) * kHistBins * (size_t)nsplit;
+    if ((e = hipMemsetAsync(gbins, 0, set_bytes * maxl, st)) != hipSuccess) return e;
+    switch (maxl) {
+        case 1: k_budget_split<1><<<nitems, kLtThreads, 0, st>>>(units, lt, items, chunk, coef, gbins); break;
+        case 2: k_budget_split<2><<<nitems, kLtThreads, 0, st>>>(units, lt, items, chunk, coef, gbins); break;
+        case 3: k_budget_split<3><<<nitems, kLtThreads, 0, st>>>(units, lt, items, chunk, coef, gbins); break;
+        default: k_budget_split<4><<<nitems, kLtThreads, 0, st>>>(units, lt, items, chunk, coef, gbins); break;
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    k_budget_pick<1><<<nsplit, kWave, 0, st>>>(lt, split_units, max_pairs, gbins, maxl, state, thresh, key);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(gbins, 0, set_bytes, st)) != hipSuccess) return e;
+    k_budget_digit<2><<<nitems, kLtThreads, 0, st>>>(units, lt, items, chunk, coef, state, gbins);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    k_budget_pick<2><<<nsplit, kWave, 0, st>>>(lt, split_units, max_pairs, gbins, maxl, state, thresh, key);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(gbins, 0, set_bytes, st)) != hipSuccess) return e;
+    k_budget_digit<3><<<nitems, kLtThreads, 0, st>>>(units, lt, items, chunk, coef, state, gbins);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    k_budget_pick<3><<<nsplit, kWave, 0, st>>>(lt, split_units, max_pairs, gbins, maxl, state, thresh, key);
+    return hipGetLastError();
+}
+
+}  // namespace wc

@@ -7,7 +7,9 @@
 // kernels and fails with WC_ERR_HIP if the device or code object is absent.
 // The _host entry points are in wc_hostpipe.cpp (wc_forward_tol_host and the
 // host-only wc_tol_threshold: wc_tolhost.cpp; wc_forward_levels_tol_host:
-// wc_leveltolhost.cpp; the host-only wc_tol_levels_threshold: wc_leveltolrule.cpp).
+// wc_leveltolhost.cpp; the host-only wc_tol_levels_threshold: wc_leveltolrule.cpp;
+// wc_forward_levels_budget_host: wc_budgethost.cpp; the host-only wc_budget_select
+// and wc_budget_thresholds: wc_budgetrule.cpp).
 //
 // Forward path per batch (wc_forward), every unit shape: K1 k_transform{,_fast}
 // -> flat coefficients in HBM scratch (sparse staging: only the flagged
@@ -279,12 +281,14 @@ int run_levels(wc_ctx* c, const LevelWork& w, bool fwd, bool with_key, const uin
 // (8-B members first; the thresholds only when the caller passes no d_thresh).
 struct LevelTolWork {
     std::vector<uint8_t> blob;
-    size_t o_items = 0, o_split = 0, o_thresh = 0;
+    size_t o_items = 0, o_split = 0, o_thresh = 0, o_tail = 0;
     uint32_t nitems = 0, nsplit = 0, chunk = 0;
 };
 
+// tol NULL: the descriptors' tolerances are 0 (the size-budget mode has none);
+// tail: bytes per unit and per split unit that a mode appends at o_tail (8-B aligned, zeroed).
 void build_leveltol(const wc_ctx* c, int n, const int32_t* levels, const double* tol, bool own_thresh,
-                    LevelTolWork* t) {
+                    LevelTolWork* t, size_t tail_unit = 0, size_t tail_split = 0) {
     const Plan& P = c->plan;
     // as stage_tol: a unit of more than opt_tol_solo flat tiles is split into runs of `chunk` tiles
     const uint32_t solo = (uint32_t)c->opt_tol_solo;
@@ -294,7 +298,8 @@ void build_leveltol(const wc_ctx* c, int n, const int32_t* levels, const double*
     std::vector<uint2> items;
     for (int u = 0; u < n; ++u) {
         const UnitDev& d = P.units[u];
-        lt[u] = {d.ncells ? rows_magic(d.nz) : 0, d.ncells ? rows_magic(d.ny) : 0, tol[u], (uint32_t)levels[u], kLtSolo};
+        lt[u] = {d.ncells ? rows_magic(d.nz) : 0, d.ncells ? rows_magic(d.ny) : 0, tol ? tol[u] : 0.0,
+                 (uint32_t)levels[u], kLtSolo};
         if (d.nftiles <= solo) continue;
         lt[u].slot = (uint32_t)split.size();
         split.push_back((uint32_t)u);
@@ -305,7 +310,9 @@ void build_leveltol(const wc_ctx* c, int n, const int32_t* levels, const double*
     t->o_items = sizeof(LtUnit) * n;
     t->o_split = t->o_items + sizeof(uint2) * items.size();
     t->o_thresh = t->o_split + 4 * split.size();
-    t->blob.assign(t->o_thresh + (own_thresh ? sizeof(float) * WC_MAX_LEVELS * n : 0), 0);
+    t->o_tail = round_up(t->o_thresh + (own_thresh ? sizeof(float) * WC_MAX_LEVELS * n : 0), 8);
+    const size_t tail = tail_unit * n + tail_split * split.size();
+    t->blob.assign(tail ? t->o_tail + tail : t->o_thresh + (own_thresh ? sizeof(float) * WC_MAX_LEVELS * n : 0), 0);
     std::memcpy(t->blob.data(), lt.data(), sizeof(LtUnit) * n);
     if (!items.empty()) std::memcpy(t->blob.data() + t->o_items, items.data(), sizeof(uint2) * items.size());
     if (!split.empty()) std::memcpy(t->blob.data() + t->o_split, split.data(), 4 * split.size());
@@ -335,6 +342,29 @@ int stage_leveltol(wc_ctx* c, int n, int maxl, const LevelTolWork& t, const uint
         e = launch_leveltol_mask(c->stream, du, lt, (const FTile*)P.d_ftiles.p, (uint32_t)P.ftiles.size(),
                                  (float*)c->coef.p, th);
     return e == hipSuccess ? WC_OK : hip_fail(c, e, "level tolerance launch");
+}
+
+// Size-budget mode, between the level passes and the emit: the radix select of
+// every unit (wc_budget.hip), then the mask pass of the tolerance mode with the
+// thresholds it found.  The tail of the blob: state[nsplit] | max_pairs[n].
+int stage_budget(wc_ctx* c, int n, int maxl, const LevelTolWork& t, const uint8_t* d_blob, float* d_thresh,
+                 uint32_t* d_key) {
+    const Plan& P = c->plan;
+    int rc;
+    if (t.nsplit && (rc = ensure(c, c->tol_bins, sizeof(uint32_t) * WC_HIST_BINS * (size_t)maxl * t.nsplit))) return rc;
+    float* th = d_thresh ? d_thresh : (float*)const_cast<uint8_t*>(d_blob + t.o_thresh);
+    const UnitDev* du = (const UnitDev*)P.d_units.p;
+    const LtUnit* lt = (const LtUnit*)d_blob;
+    BudgetState* state = (BudgetState*)const_cast<uint8_t*>(d_blob + t.o_tail);
+    const uint32_t* maxp = (const uint32_t*)(d_blob + t.o_tail + sizeof(BudgetState) * t.nsplit);
+    StageTimer timer(c, WC_STAGE_TOL);
+    hipError_t e = launch_budget(c->stream, du, n, lt, maxp, (const uint2*)(d_blob + t.o_items), t.nitems, t.chunk,
+                                 (const uint32_t*)(d_blob + t.o_split), t.nsplit, maxl, (const float*)c->coef.p,
+                                 (uint32_t*)c->tol_bins.p, state, th, d_key);
+    if (e == hipSuccess)
+        e = launch_leveltol_mask(c->stream, du, lt, (const FTile*)P.d_ftiles.p, (uint32_t)P.ftiles.size(),
+                                 (float*)c->coef.p, th);
+    return e == hipSuccess ? WC_OK : hip_fail(c, e, "size budget launch");
 }
 
 bool single_level(const int32_t* levels, int n) {
@@ -996,6 +1026,48 @@ int wc_forward_levels_tol(wc_ctx* c, const void* d_cells, int dtype, const wc_un
     if ((rc = upload_levels(c, n, levels, &w, t.blob.data(), t.blob.size(), &d_blob)) ||
         (rc = stage_transform(c, d_cells, dtype, 0.0, false)) || (rc = run_levels(c, w, true, false)) ||
         (rc = stage_leveltol(c, n, w.maxl, t, (const uint8_t*)d_blob, d_thresh, d_bound)) ||
+        (rc = stage_emit(c, n, 0.0, &zero, d_payload, d_offsets, d_kept)))
+        return rc;
+    StageTimer timer(c, WC_STAGE_LEVELS);
+    hipError_t e = launch_level_headers(c->stream, (const UnitDev*)c->plan.d_units.p, w.hdr, w.nhdr, d_payload);
+    return e == hipSuccess ? WC_OK : hip_fail(c, e, "level header launch");
+}
+
+// Multi-level forward under a pair budget per unit: wc_forward_levels' staging
+// and level passes, the radix select and the mask pass on the final array, the
+// unchanged emit with threshold 0.0f, the header patch.  No device-to-host read
+// anywhere: the select's state stays on the device.  Leaves nothing staged.
+int wc_forward_levels_budget(wc_ctx* c, const void* d_cells, int dtype, const wc_unit* units, int n,
+                             const int32_t* levels, const uint32_t* max_pairs, uint8_t* d_payload, uint64_t cap,
+                             uint64_t* d_offsets, uint32_t* d_kept, float* d_thresh, uint32_t* d_key) {
+    if (!c) return WC_ERR_INVALID;
+    int rc;
+    if ((rc = validate_units(c, units, n))) return rc;
+    if (dtype != WC_F32 && dtype != WC_F64) return fail(c, WC_ERR_INVALID, "dtype");
+    if (n == 0) return WC_OK;
+    if (!d_cells || !d_payload || !d_offsets || !d_kept || !max_pairs) return fail(c, WC_ERR_INVALID, "null buffer");
+    std::vector<int32_t> ones;
+    if (!levels) {
+        ones.assign(n, 1);
+        levels = ones.data();
+    }
+    if ((rc = validate_budget(c, units, n, levels))) return rc;
+    if (cap < wc_payload_bound(units, n)) return fail(c, WC_ERR_INVALID, "payload_capacity < wc_payload_bound");
+    if ((rc = check_aligned(c, d_cells, "cells")) || (rc = check_aligned(c, d_payload, "payload")) ||
+        (rc = check_aligned(c, d_offsets, "offsets", 8)) || (rc = check_aligned(c, d_kept, "kept", 4)) ||
+        (rc = check_aligned(c, d_thresh, "thresh", 4)) || (rc = check_aligned(c, d_key, "key", 4)))
+        return rc;
+    if ((rc = set_device(c)) || (rc = get_plan(c, units, n))) return rc;
+    if ((rc = ensure_scratch(c))) return rc;
+    LevelWork w;
+    LevelTolWork t;
+    build_leveltol(c, n, levels, nullptr, !d_thresh, &t, sizeof(uint32_t), sizeof(BudgetState));
+    std::memcpy(t.blob.data() + t.o_tail + sizeof(BudgetState) * t.nsplit, max_pairs, sizeof(uint32_t) * n);
+    const void* d_blob = nullptr;
+    const float zero = 0.0f;  // the mask pass has applied the thresholds: the emit keeps every non-zero
+    if ((rc = upload_levels(c, n, levels, &w, t.blob.data(), t.blob.size(), &d_blob)) ||
+        (rc = stage_transform(c, d_cells, dtype, 0.0, false)) || (rc = run_levels(c, w, true, false)) ||
+        (rc = stage_budget(c, n, w.maxl, t, (const uint8_t*)d_blob, d_thresh, d_key)) ||
         (rc = stage_emit(c, n, 0.0, &zero, d_payload, d_offsets, d_kept)))
         return rc;
     StageTimer timer(c, WC_STAGE_LEVELS);

@@ -23,6 +23,10 @@
 //                    multi-level transform: the per-level selection rule (plain
 //                    C++, linked alone by tests/cpp/test_leveltol.cpp) and
 //                    wc_forward_levels_tol_host
+//   wc_budgetrule.cpp / wc_budgethost.cpp  the size-budget mode: the exact top-K
+//                    selection rule on one unit's final array (plain C++, linked
+//                    alone by tests/cpp/test_budget.cpp), the argument checks
+//                    and wc_forward_levels_budget_host
 //   wc_coarsehost.cpp host side of the reduced-resolution inverse: wc_coarse_units,
 //                    the argument checks and wc_inverse_coarse_host
 //   wc_regionrule.cpp / wc_regionhost.cpp  the sub-box inverse: wc_region_align
@@ -94,6 +98,11 @@ hipError_t launch_leveltol(hipStream_t, const UnitDev*, int, const LtUnit*, cons
                            uint32_t* gbins, float* thresh, double* bound);
 hipError_t launch_leveltol_mask(hipStream_t, const UnitDev*, const LtUnit*, const FTile*, uint32_t ntiles, float* coef,
                                 const float* thresh);
+// wc_budget.hip: the radix select of the size-budget mode (thresh / key per unit;
+// launch_leveltol_mask then applies the thresholds)
+hipError_t launch_budget(hipStream_t, const UnitDev*, int, const LtUnit*, const uint32_t* max_pairs, const uint2* items,
+                         uint32_t nitems, uint32_t chunk, const uint32_t* split_units, uint32_t nsplit, int maxl,
+                         const float* coef, uint32_t* gbins, BudgetState* state, float* thresh, uint32_t* key);
 // wc_coarse.hip: the corner decode (over a prefix of the full plan's decode
 // tiles) into the compact corners, and the copy of the corners of the units with
 // r == L to their Box3D cells (over the derived plan's flat tiles)
@@ -219,8 +228,8 @@ struct wc_ctx {
     hipEvent_t tol_ev = nullptr;
     bool tol_ev_live = false;
     wc::DevBuf tol_in;            // tol[n] | slot[n] | split_units[nsplit] | items[nitems] | thresh[n]
-    wc::DevBuf tol_bins;          // kHistBins uint32 per split unit (none without split units)
-    wc::DevBuf h_thresh, h_bound; // wc_forward_tol_host: per-unit thresholds and bounds
+    wc::DevBuf tol_bins;          // kHistBins uint32 per split unit and level (none without split units)
+    wc::DevBuf h_thresh, h_bound; // wc_forward_tol_host: per-unit thresholds and bounds (_budget_host: the keys)
     // multi-level mode (wc_forward_levels / wc_inverse_levels): the side scratch
     // of the level passes (coef_extent / 8 floats); the call's levels and work
     // lists go through the same pinned block and tol_in
@@ -279,6 +288,9 @@ int validate_tol(wc_ctx* c, const wc_unit* units, int n, const double* tol);
 // wc_levelshost.cpp
 int validate_levels(wc_ctx* c, const wc_unit* units, int n, const int32_t* levels);
 std::vector<int> level_runs(const wc_ctx* c, const wc_unit* units, int n);
+
+// wc_budgethost.cpp
+int validate_budget(wc_ctx* c, const wc_unit* units, int n, const int32_t* levels);
 
 // wc_coarsehost.cpp
 int validate_coarse(wc_ctx* c, const wc_unit* units, int n, const int32_t* levels, const int32_t* reduce,

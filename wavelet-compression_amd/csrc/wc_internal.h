@@ -136,6 +136,16 @@ struct LtUnit {
 static_assert(sizeof(LtUnit) == 32, "descriptor of 8-B members first");
 constexpr uint32_t kLtSolo = 0xffffffffu;
 
+// The radix select of one split unit in the size-budget mode (wc_budget.hip),
+// between its passes: it stays on the device.
+struct BudgetState {
+    uint32_t prefix;  // the key's digits found so far (12, then 24 bits)
+    uint32_t above;   // candidates whose key is above every key with this prefix
+    uint32_t done;    // 1: thresh / key are written, the later passes skip the unit
+    uint32_t pad;
+};
+static_assert(sizeof(BudgetState) == 16, "one 16-B load");
+
 // Per-unit skip words (bad[u]) that k_decode<true> and k_decode_corner leave for
 // the launches after them: the level passes and k_inverse{,_fast}<true> skip a
 // unit unless its word is kUnitRun.
