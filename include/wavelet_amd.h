@@ -675,6 +675,115 @@ int wc_inverse_region_host(wc_ctx* ctx, const uint8_t* payload, const uint64_t* 
                            const int32_t* levels, const int32_t* reduce, const wc_region* regions,
                            const wc_unit* out_units, float* out);
 
+/* Opt-in packed payloads (NOT a reference format): a smaller way to STORE a
+ * payload's kept coefficients.  A standard payload spends 8 bytes per pair, an
+ * int32 run and an fp32 value; a packed unit stores each chunk of 64 pairs as
+ * bit planes of the runs at the chunk's own width and as the top 2, 3 or 4 bytes
+ * of the values in byte planes.  No decoder reads the packed format: wc_unpack
+ * restores standard payloads and every decoder reads those unchanged.  Every
+ * existing entry point rejects a packed unit (WC_ERR_FORMAT), its ncoeff field
+ * being neither W*H*D nor -2..-4.
+ *
+ * Format of one unit (integers little-endian).  V = value bytes, 2..4; L = the
+ * source payload's levels, 1..WC_MAX_LEVELS; n = its nrle; nch = ceil(n / 64);
+ * m_c = the pairs of chunk c, 64 for every chunk but the last, n - 64 (nch - 1)
+ * for the last; pad8 rounds up to a multiple of 8.
+ *   1. Header, 20 bytes: int32 W, H, D, tag, n with tag = -(16 V + L), -33..-68.
+ *   2. Width table, nch bytes: w_c = bit_length(OR of the chunk's runs), 0..31;
+ *      zero-padded to pad8(nch) bytes (readers ignore the pad).
+ *   3. The chunks in order, each a run area and a value area.  Run area: w_c
+ *      planes of ceil(m_c / 8) bytes; bit j % 8 of byte j / 8 of plane b is bit b
+ *      of run j, unused bits 0 (a full chunk's plane is a wave64 ballot).  Value
+ *      area: V planes of m_c bytes; byte j of plane p is byte 3 - p of the uint32
+ *      q(value j): plane 0 is the sign-and-exponent byte.
+ *   4. A unit starts at an offset == 4 (mod 8), as payload slots do; every full
+ *      chunk then starts 8-byte aligned.
+ *   5. The packed length, 20 + pad8(nch) + sum_c (w_c ceil(m_c / 8) + V m_c),
+ *      follows from the header and the table alone (wc_packed_size).
+ * Value rule q (integers only: host, device and numpy give the same bits).
+ * s = 8 (4 - V); b = the value's bits, m = b & 0x7FFFFFFF, sign = b & 0x80000000.
+ *   V = 4: q = b.  NaN (m > 0x7F800000): q = (b | 0x00400000) with the low s
+ *   bits cleared (still a NaN).  inf: unchanged.  Otherwise r = (m + (1 << (s-1))
+ *   - 1 + ((m >> s) & 1)) with the low s bits cleared: round to nearest even, a
+ *   carry into the exponent wanted; if r >= 0x7F800000, r = m with the low s bits
+ *   cleared (a finite value stays finite); q = sign | r.  A subnormal may round
+ *   to +-0; the pair stays, with value +-0.  q(q(x)) = q(x).
+ * Error: the level-l basis vectors are orthogonal with squared norm 8^l and
+ * |q(v) - v| <= 2^(s-24) |v|, so for finite values
+ *   || decode(q(p)) - decode(p) ||_2 <= 2^(s-24) || decode(p) ||_2
+ * up to the decoder's own fp32 rounding: 2^-8 of the box's norm at V = 2, 2^-16 at
+ * V = 3, nothing at V = 4.
+ * Slots: the worst-case packed unit of N cells is S(N) = 20 + pad8(ceil(N / 64))
+ * + 31 ceil(N / 8) + V N; unit u's slot is the prefix of pad8(S(N) + 4) of the
+ * units before it, starting at 4 (the forward's scheme); wc_packed_bound gives
+ * the capacity.
+ *
+ * Host-only rule (plain C++, no device):
+ *   wc_pack_value: q.  vbytes outside 2..4: the bits unchanged.
+ *   wc_packed_tag: the tag; 0 for levels or vbytes out of range.
+ *   wc_payload_packed: *levels and *vbytes of a 20-byte header; *vbytes = 0 for a
+ *     standard or multi-level header (then as wc_payload_levels).  WC_ERR_FORMAT
+ *     for any other header.
+ *   wc_packed_size: *bytes = the length of the packed unit at `unit`, of which
+ *     `avail` bytes may be read: WC_ERR_INVALID if that is less than the header
+ *     and the padded table; WC_ERR_FORMAT for a header that is not a packed one,
+ *     n above the cell count or a width above 31.
+ *   wc_pack_unit / wc_unpack_unit: one unit between the two forms.  WC_ERR_FORMAT
+ *     for what the device calls refuse (below); WC_ERR_INVALID for null or short
+ *     buffers or vbytes outside 2..4; nothing is written then.
+ * Device calls, asynchronous on the context's stream, nothing read back:
+ *   wc_pack: standard payloads at d_payload + d_offsets[u] (any multiple of 4;
+ *     the layout of wc_forward or of the _host forms) -> packed units in their
+ *     slots.  d_packed_offsets: n + 1 uint64, unit u's slot and, at n, the end of
+ *     the last unit's bytes; d_packed_bytes: n uint64, each unit's exact length
+ *     (0 for a refused unit).  packed_capacity >= wc_packed_bound.  Nothing is
+ *     written outside a unit's exact length.
+ *   wc_unpack: packed units at d_packed + d_packed_offsets[u] (each == 4 mod 8;
+ *     slots or the dense layout of wc_pack_host) -> standard payloads in the
+ *     forward's slot layout (payload_capacity >= wc_payload_bound; d_offsets n + 1,
+ *     d_kept n, as wc_forward writes them).  Values are q(v), runs unchanged, the
+ *     header's ncoeff is W*H*D again, or -L for L >= 2.  At V = 4 the payload is
+ *     byte for byte the source.  Nothing at or past packed_capacity is read.
+ *   Both take units of at most WC_PACK_MAX_CELLS cells: a workgroup finds its
+ *   place by summing the width table before it, which no workgroup has to wait
+ *   for but costs n^2 / 2^18 table bytes on a unit of n pairs.
+ * Refusals.  On the device (WC_ERR_FORMAT at the next wc_synchronize; the other
+ * units of the call are transcoded, nothing is written outside the refused
+ * unit's slot): in wc_pack a source header that is not a standard or multi-level
+ * header of its unit, nrle above the cell count, a negative run; in wc_unpack an
+ * offset that is not 4 (mod 8), a header or tag that is not a packed one of its
+ * unit, n above the cell count, a width above 31, a unit whose length from
+ * header and table would pass packed_capacity.  Before anything is launched
+ * (WC_ERR_INVALID, outputs untouched): null buffers, a capacity below its bound,
+ * vbytes outside 2..4, a unit above WC_PACK_MAX_CELLS cells.
+ *   wc_pack_host / wc_unpack_host: host buffers; one upload, the device call, the
+ *     slots packed densely on the device as wc_forward_host does, one download.
+ *     They are NOT pipelined over WC_OPT_HOST_CHUNK runs, and they cost one more
+ *     crossing of the payload bytes than a forward that packed before its
+ *     download would.  wc_pack_host: packed_offsets (n + 1; each == 4 mod 8,
+ *     unit u + 1 at pad8 of unit u's length after unit u; [n] = the end of the
+ *     last unit's bytes) and packed_bytes (n); packed_capacity >= packed_offsets[n],
+ *     at most wc_packed_bound.  wc_unpack_host: payload, offsets and kept as
+ *     wc_forward_host returns them.  A refused unit fails the call
+ *     (WC_ERR_FORMAT) and leaves the outputs untouched. */
+#define WC_PACK_MAX_CELLS (1 << 21)
+uint32_t wc_pack_value(uint32_t bits, int vbytes);
+int32_t wc_packed_tag(int levels, int vbytes);
+int wc_payload_packed(const uint8_t* header, size_t len, int* levels, int* vbytes);
+int wc_packed_size(const uint8_t* unit, size_t avail, uint64_t* bytes);
+int wc_pack_unit(const uint8_t* payload, size_t len, int vbytes, uint8_t* out, size_t cap, size_t* written);
+int wc_unpack_unit(const uint8_t* packed, size_t len, uint8_t* out, size_t cap, size_t* written);
+int wc_packed_bound(const wc_unit* units, int n, int vbytes, uint64_t* bytes);
+int wc_pack(wc_ctx* ctx, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n, int vbytes,
+            uint8_t* d_packed, uint64_t packed_capacity, uint64_t* d_packed_offsets, uint64_t* d_packed_bytes);
+int wc_unpack(wc_ctx* ctx, const uint8_t* d_packed, const uint64_t* d_packed_offsets, uint64_t packed_capacity,
+              const wc_unit* units, int n, uint8_t* d_payload, uint64_t payload_capacity, uint64_t* d_offsets,
+              uint32_t* d_kept);
+int wc_pack_host(wc_ctx* ctx, const uint8_t* payload, const uint64_t* offsets, const wc_unit* units, int n, int vbytes,
+                 uint8_t* packed, uint64_t packed_capacity, uint64_t* packed_offsets, uint64_t* packed_bytes);
+int wc_unpack_host(wc_ctx* ctx, const uint8_t* packed, const uint64_t* packed_offsets, const wc_unit* units, int n,
+                   uint8_t* payload, uint64_t payload_capacity, uint64_t* offsets, uint32_t* kept);
+
 /* Transform only: cells -> flat fp32 coefficients (x-slowest order), written
  * at the same element offsets as the cells (d_flat has the cell buffer's extent). */
 int wc_decompose(wc_ctx* ctx, const void* d_cells, int dtype, const wc_unit* units, int n,
@@ -772,7 +881,8 @@ int wc_decompose_host(wc_ctx* ctx, const void* cells, int dtype, const wc_unit* 
                                  wc_forward_levels_budget */
 #define WC_STAGE_LEVELS 8    /* level passes, key pass and header patch of the multi-level mode (wc_forward_levels,
                                  wc_inverse_levels) */
-#define WC_NUM_STAGES 9
+#define WC_STAGE_PACK 9      /* packed payloads: k_pack_widths + k_pack_body (wc_pack), k_unpack (wc_unpack) */
+#define WC_NUM_STAGES 10
 int wc_profile_enable(wc_ctx* ctx, int on);
 int wc_profile_read(wc_ctx* ctx, double* total_ms, uint32_t* launches, int nstages);
 

@@ -37,6 +37,13 @@ struct Config {
     // together with rmse=.  1: not given.  levels_error: given but unusable.
     int levels = 1;
     bool levels_error = false;
+    // Not a reference parameter: `pack=V` (2, 3 or 4) makes -c and -estimate write
+    // packed units with V value bytes (wc_pack_host on each chunk's payloads,
+    // before the xz stage; include/wavelet_amd.h "Opt-in packed payloads").  It
+    // combines with levels= and with rmse=.  -d recognises such files by their
+    // headers.  0: not given.  pack_error: given but unusable.
+    int pack = 0;
+    bool pack_error = false;
 };
 
 // Stand-in for amrex::Initialize's ParmParse setup: parse `name=value ...`

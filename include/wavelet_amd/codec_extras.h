@@ -71,4 +71,19 @@ std::vector<CompressedWavelet> compress_rmse(multiBox3D& box, std::vector<int> c
 std::vector<CompressedWavelet> compress_budget(multiBox3D& box, std::vector<int> components, int levels, double ratio,
                                                int time, int level, int box_index, std::string compressed_dir);
 
+// compress() whose files hold packed units (GPU, wc_pack_host after the forward; not
+// a reference format, include/wavelet_amd.h "Opt-in packed payloads"): each kept
+// value stored in its top `vbytes` bytes (4: lossless; 3, 2: rounded to nearest even,
+// an added error of at most 2^-16 or 2^-8 of the box's norm), the runs as bit planes.
+// Same file names; decompress(), decompress_coarse() and decompress_region() recognise
+// such files by their headers and unpack them first (wc_unpack_host).  The returned
+// structs describe the payloads before packing.  vbytes outside 2..4 or a component
+// of more than WC_PACK_MAX_CELLS cells: it exits with a message, as the other errors do.
+std::vector<CompressedWavelet> compress_packed(multiBox3D& box, std::vector<int> components, double keep, int vbytes,
+                                               int time, int level, int box_index, std::string compressed_dir);
+
+// The standard payload of a file's bytes after xz: a packed unit unpacked on the GPU
+// (wc_unpack_host), anything else returned as it is.
+std::string standard_payload(std::string payload);
+
 }  // namespace wavelet_amd

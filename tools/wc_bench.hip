@@ -386,7 +386,7 @@ int main(int argc, char** argv) {
     CK(hipMemcpy(hk.data(), kept, 4 * boxes, hipMemcpyDeviceToHost));
     double ksum = 0;
     for (uint32_t k : hk) ksum += k;
-    const char* names[WC_NUM_STAGES] = {"transform", "emit", "decode", "inverse", "rmse", "hist", "pairs", "tol", "levels"};
+    const char* names[WC_NUM_STAGES] = {"transform", "emit", "decode", "inverse", "rmse", "hist", "pairs", "tol", "levels", "pack"};
     std::printf("{\"boxes\": %d, \"dim\": %d, \"dtype\": \"%s\", \"keep\": %.17g, \"steps\": %d, "
                 "\"ms_per_step\": %.4f, \"cells_per_s\": %.6e, \"kept_fraction\": %.6f, \"payload_bytes\": %llu, "
                 "\"ordered\": %d, \"sparse\": %d, \"rows\": %d, \"rix\": [%d, %d, %d], \"paths_identical\": %d, \"stage_ms\": {",

@@ -37,8 +37,11 @@ EXPORTED = (
     "wc_tol_levels_threshold", "wc_forward_levels_tol", "wc_forward_levels_tol_host",
     "wc_region_align", "wc_region_units", "wc_inverse_region", "wc_inverse_region_host",
     "wc_budget_thresholds", "wc_budget_select", "wc_forward_levels_budget", "wc_forward_levels_budget_host",
+    "wc_pack_value", "wc_packed_tag", "wc_payload_packed", "wc_packed_size", "wc_pack_unit", "wc_unpack_unit",
+    "wc_packed_bound", "wc_pack", "wc_unpack", "wc_pack_host", "wc_unpack_host",
 )
 WC_MAX_LEVELS = 4  # levels of the opt-in multi-level transform (1 = the reference's codec)
+WC_PACK_MAX_CELLS = 1 << 21  # the largest unit wc_pack / wc_unpack take (the host rule has no limit)
 WC_LTOL_SHIFT = 24  # bins between the walks of two adjacent levels in the multi-level RMSE-tolerance rule
 WC_OPT_SPARSE = 12   # sparse coefficient staging in the forward (default 1)
 WC_OPT_ORDERED = 13  # look-back tile index from the launch order (1, default) or per-unit tickets (0)
@@ -57,7 +60,7 @@ WC_OPT_HOST_THP = 28  # _host calls: advise huge pages on those destinations (de
 WC_OPT_TOL_SOLO_TILES = 30  # RMSE-tolerance mode: flat tiles a unit may have and still be binned by one workgroup (default 64)
 
 # Stage ids of wc_profile_read (include/wavelet_amd.h WC_STAGE_*).
-STAGES = ("transform", "emit", "decode", "inverse", "rmse", "hist", "pairs", "tol", "levels")
+STAGES = ("transform", "emit", "decode", "inverse", "rmse", "hist", "pairs", "tol", "levels", "pack")
 
 
 class WcUnit(ctypes.Structure):
@@ -162,6 +165,17 @@ def load_library() -> ctypes.CDLL:
         "wc_region_units": (i32, [up, rp, vp, i32, up, ctypes.POINTER(u64)]),
         "wc_inverse_region": (i32, [vp, vp, vp, up, i32, vp, vp, rp, up, vp]),
         "wc_inverse_region_host": (i32, [vp, vp, vp, up, i32, vp, vp, rp, up, vp]),
+        "wc_pack_value": (ctypes.c_uint32, [ctypes.c_uint32, i32]),
+        "wc_packed_tag": (ctypes.c_int32, [i32, i32]),
+        "wc_payload_packed": (i32, [vp, ctypes.c_size_t, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
+        "wc_packed_size": (i32, [vp, ctypes.c_size_t, ctypes.POINTER(u64)]),
+        "wc_pack_unit": (i32, [vp, ctypes.c_size_t, i32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+        "wc_unpack_unit": (i32, [vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+        "wc_packed_bound": (i32, [up, i32, i32, ctypes.POINTER(u64)]),
+        "wc_pack": (i32, [vp, vp, vp, up, i32, i32, vp, u64, vp, vp]),
+        "wc_unpack": (i32, [vp, vp, vp, u64, up, i32, vp, u64, vp, vp]),
+        "wc_pack_host": (i32, [vp, vp, vp, up, i32, i32, vp, u64, vp, vp]),
+        "wc_unpack_host": (i32, [vp, vp, vp, up, i32, vp, u64, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -416,6 +430,22 @@ class Context:
                                               None if rd is None else rd.ctypes.data, make_regions(regions, n),
                                               out_units, ctypes.c_void_p(d_out)))
 
+    def pack(self, d_payload: int, d_offsets: int, units, n: int, vbytes: int, d_packed: int, capacity: int,
+             d_packed_offsets: int, d_packed_bytes: int):
+        """wc_pack: standard payloads -> packed units in their slots (packed_bound);
+        d_packed_offsets: n + 1 uint64, d_packed_bytes: n uint64 (exact lengths)."""
+        self._check(self._L.wc_pack(self._h, ctypes.c_void_p(d_payload), ctypes.c_void_p(d_offsets), units, n,
+                                    int(vbytes), ctypes.c_void_p(d_packed), int(capacity),
+                                    ctypes.c_void_p(d_packed_offsets), ctypes.c_void_p(d_packed_bytes)))
+
+    def unpack(self, d_packed: int, d_packed_offsets: int, packed_capacity: int, units, n: int, d_payload: int,
+               capacity: int, d_offsets: int, d_kept: int):
+        """wc_unpack: packed units -> standard payloads in the forward's slot layout
+        (payload_bound), values q(v), runs unchanged."""
+        self._check(self._L.wc_unpack(self._h, ctypes.c_void_p(d_packed), ctypes.c_void_p(d_packed_offsets),
+                                      int(packed_capacity), units, n, ctypes.c_void_p(d_payload), int(capacity),
+                                      ctypes.c_void_p(d_offsets), ctypes.c_void_p(d_kept)))
+
     def decompose(self, d_cells: int, dtype: int, units, n: int, d_flat: int):
         self._check(self._L.wc_decompose(self._h, ctypes.c_void_p(d_cells), dtype, units, n,
                                          ctypes.c_void_p(d_flat)))
@@ -620,6 +650,33 @@ class Context:
                                                    out_units, out.ctypes.data))
         return out[:extent]
 
+    def pack_host(self, payload: np.ndarray, offsets: np.ndarray, units, n: int, vbytes: int):
+        """wc_pack_host: standard payloads (host) -> (packed uint8, packed_offsets
+        uint64[n + 1], packed_bytes uint64[n]); unit u's packed bytes are
+        packed[packed_offsets[u] : packed_offsets[u] + packed_bytes[u]]."""
+        p = np.ascontiguousarray(payload, dtype=np.uint8)
+        o = np.ascontiguousarray(offsets, dtype=np.uint64)
+        cap = packed_bound(units, n, vbytes)
+        packed = np.empty(cap, np.uint8)
+        poff = np.zeros(n + 1, np.uint64)
+        pbytes = np.zeros(max(n, 1), np.uint64)
+        self._check(self._L.wc_pack_host(self._h, p.ctypes.data, o.ctypes.data, units, n, int(vbytes),
+                                         packed.ctypes.data, cap, poff.ctypes.data, pbytes.ctypes.data))
+        return packed[:int(poff[n])] if n else packed[:0], poff, pbytes[:n]
+
+    def unpack_host(self, packed: np.ndarray, packed_offsets: np.ndarray, units, n: int):
+        """wc_unpack_host: packed units (host, each offset == 4 mod 8) -> (payload,
+        offsets, kept) as forward_host returns them."""
+        p = np.ascontiguousarray(packed, dtype=np.uint8)
+        o = np.ascontiguousarray(packed_offsets, dtype=np.uint64)
+        cap = payload_bound(units, n)
+        payload = np.empty(cap, np.uint8)
+        offsets = np.zeros(n + 1, np.uint64)
+        kept = np.zeros(max(n, 1), np.uint32)
+        self._check(self._L.wc_unpack_host(self._h, p.ctypes.data, o.ctypes.data, units, n, payload.ctypes.data, cap,
+                                           offsets.ctypes.data, kept.ctypes.data))
+        return payload, offsets, kept[:n]
+
     def forward_host_units(self, boxes, units, n: int, keep: float):
         """wc_forward_host_units: unit u's cells from boxes[u] (its own host
         array, all float32 or all float64) -> (payload, offsets, kept)."""
@@ -780,6 +837,71 @@ def payload_levels(header) -> int:
     if rc:
         raise WaveletError(rc, "wc_payload_levels: not a payload header")
     return int(lv.value)
+
+
+def pack_value(bits: int, vbytes: int) -> int:
+    """wc_pack_value (host only): q, the fp32 bits rounded to nearest even at vbytes bytes."""
+    return int(load_library().wc_pack_value(int(bits) & 0xFFFFFFFF, int(vbytes)))
+
+
+def packed_tag(levels: int, vbytes: int) -> int:
+    """wc_packed_tag (host only): -(16 * vbytes + levels); 0 for values out of range."""
+    return int(load_library().wc_packed_tag(int(levels), int(vbytes)))
+
+
+def payload_packed(header):
+    """wc_payload_packed (host only): (levels, vbytes) of a unit from its first 20
+    bytes; vbytes = 0 for a standard or multi-level payload."""
+    h = np.frombuffer(bytes(header[:20]), dtype=np.uint8)
+    lv, vb = ctypes.c_int(), ctypes.c_int()
+    rc = load_library().wc_payload_packed(h.ctypes.data, h.size, ctypes.byref(lv), ctypes.byref(vb))
+    if rc:
+        raise WaveletError(rc, "wc_payload_packed: neither a payload header nor a packed one")
+    return int(lv.value), int(vb.value)
+
+
+def packed_size(unit) -> int:
+    """wc_packed_size (host only): the length of the packed unit at the start of
+    `unit`, from its header and width table."""
+    b = np.frombuffer(bytes(unit), dtype=np.uint8)
+    out = ctypes.c_uint64()
+    rc = load_library().wc_packed_size(b.ctypes.data, b.size, ctypes.byref(out))
+    if rc:
+        raise WaveletError(rc, "wc_packed_size: a short buffer or a malformed packed unit")
+    return int(out.value)
+
+
+def packed_bound(units, n: int, vbytes: int) -> int:
+    """wc_packed_bound (host only): the capacity wc_pack needs (the slots' end)."""
+    out = ctypes.c_uint64()
+    rc = load_library().wc_packed_bound(units, n, int(vbytes), ctypes.byref(out))
+    if rc:
+        raise WaveletError(rc, "wc_packed_bound: negative dims or vbytes outside 2..4")
+    return int(out.value)
+
+
+def pack_unit(payload, vbytes: int) -> bytes:
+    """wc_pack_unit (host only): one standard payload -> its packed unit."""
+    p = np.frombuffer(bytes(payload), dtype=np.uint8)
+    n = (p.size - 20) // 8 if p.size >= 20 else 0
+    out = np.empty(20 + (n // 64 + 8) + 31 * (n // 8 + 1) + 4 * n + 16, np.uint8)
+    w = ctypes.c_size_t()
+    rc = load_library().wc_pack_unit(p.ctypes.data, p.size, int(vbytes), out.ctypes.data, out.size, ctypes.byref(w))
+    if rc:
+        raise WaveletError(rc, "wc_pack_unit: a malformed payload, a short buffer or vbytes outside 2..4")
+    return out[:w.value].tobytes()
+
+
+def unpack_unit(packed) -> bytes:
+    """wc_unpack_unit (host only): one packed unit -> its standard payload (values q(v))."""
+    p = np.frombuffer(bytes(packed), dtype=np.uint8)
+    nrle = int(np.frombuffer(p[16:20].tobytes(), np.int32)[0]) if p.size >= 20 else 0
+    out = np.empty(20 + 8 * min(max(nrle, 0), p.size), np.uint8)  # a pair takes at least two packed bytes
+    w = ctypes.c_size_t()
+    rc = load_library().wc_unpack_unit(p.ctypes.data, p.size, out.ctypes.data, out.size, ctypes.byref(w))
+    if rc:
+        raise WaveletError(rc, "wc_unpack_unit: a malformed or short packed unit")
+    return out[:w.value].tobytes()
 
 
 def tol_threshold(counts: np.ndarray, ncoeff: int, tol: float):

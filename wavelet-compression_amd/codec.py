@@ -120,8 +120,64 @@ def _pairs_need32(vals: np.ndarray) -> bool:
     return bool(vals.size and np.any(np.abs(vals.astype(np.float64)) > 32767))
 
 
+def _laid_out(units_bytes: Sequence[bytes]):
+    """The units back to back in one buffer, each at an offset == 4 (mod 8) -> (buffer, offsets)."""
+    offsets = np.zeros(max(len(units_bytes), 1), np.uint64)
+    cur = 4
+    for i, p in enumerate(units_bytes):
+        offsets[i] = cur
+        cur += (len(p) + 4 + 7) // 8 * 8
+    buf = np.zeros(cur + 8, np.uint8)
+    for i, p in enumerate(units_bytes):
+        o = int(offsets[i])
+        buf[o:o + len(p)] = np.frombuffer(p, np.uint8)
+    return buf, offsets
+
+
+def _header_dims(units_bytes: Sequence[bytes]) -> list:
+    return [tuple(int(v) for v in np.frombuffer(p[:12], "<i4")) for p in units_bytes]
+
+
+def pack_payloads(payloads: Sequence[bytes], pack: int, device: int = 0) -> List[bytes]:
+    """Standard payloads -> packed units with `pack` value bytes (2, 3 or 4; not a
+    reference format, include/wavelet_amd.h "Opt-in packed payloads"): one
+    wc_pack_host call.  pack = 4 is lossless; 3 and 2 round every kept value to
+    its top 3 or 2 bytes (an added error of at most 2^-16 or 2^-8 of the box's
+    norm)."""
+    if isinstance(pack, bool) or pack not in (2, 3, 4):
+        raise ValueError(f"pack: 2, 3 or 4 value bytes, not {pack!r}")
+    if not payloads:
+        return []
+    units, n, _ = capi.make_units(_header_dims(payloads))
+    buf, offsets = _laid_out(payloads)
+    packed, poff, pbytes = context(device).pack_host(buf, offsets, units, n, int(pack))
+    return [packed[int(poff[i]):int(poff[i]) + int(pbytes[i])].tobytes() for i in range(n)]
+
+
+def unpack_payloads(packed: Sequence[bytes], device: int = 0) -> List[bytes]:
+    """Packed units -> standard payloads (values q(v), runs unchanged): one wc_unpack_host call."""
+    if not packed:
+        return []
+    units, n, _ = capi.make_units(_header_dims(packed))
+    buf, offsets = _laid_out(packed)
+    payload, poff, kept = context(device).unpack_host(buf, offsets, units, n)
+    return [capi.unit_payload(payload, poff, kept, i) for i in range(n)]
+
+
+def _standard_payloads(payloads: Sequence[bytes], device: int = 0) -> List[bytes]:
+    """The list with its packed units (capi.payload_packed) unpacked; a list without any is returned as it is."""
+    which = [i for i, p in enumerate(payloads) if len(p) >= 20 and int(np.frombuffer(p[12:16], "<i4")[0]) < -capi.WC_MAX_LEVELS
+             and capi.payload_packed(p)[1]]
+    if not which:
+        return list(payloads)
+    out = list(payloads)
+    for i, p in zip(which, unpack_payloads([payloads[i] for i in which], device)):
+        out[i] = p
+    return out
+
+
 def compress_payloads(boxes: Sequence[np.ndarray], keep: float, device: int = 0, levels: int = 1, rmse=None,
-                      max_bytes=None, ratio=None):
+                      max_bytes=None, ratio=None, pack=None):
     """Batched forward path: list of Box3D -> list of serialized payload bytes.
 
     One wc_forward_host_units call for the whole list (all units in one launch
@@ -137,7 +193,14 @@ def compress_payloads(boxes: Sequence[np.ndarray], keep: float, device: int = 0,
     // 8 largest weighted coefficients (wc_forward_levels_budget_host; ties at
     the boundary are all dropped).  ratio: max_bytes = max(20, floor(4 * N /
     ratio)) per box of N cells.  rmse, max_bytes and ratio exclude each other.
-    The payload format is the same."""
+    The payload format is the same.  pack (not a reference parameter; None, 2,
+    3 or 4): applied after any of the above, the payloads are returned as packed
+    units with that many value bytes (pack_payloads); max_bytes and ratio keep
+    meaning the bytes of the STANDARD payload, not of the packed unit."""
+    if pack is not None:
+        if isinstance(pack, bool) or pack not in (2, 3, 4):
+            raise ValueError(f"pack: None, 2, 3 or 4 value bytes, not {pack!r}")
+        return pack_payloads(compress_payloads(boxes, keep, device, levels, rmse, max_bytes, ratio), pack, device)
     if sum(v is not None for v in (rmse, max_bytes, ratio)) > 1:
         raise ValueError("rmse, max_bytes and ratio are mutually exclusive")
     dims = [_box_dims(b) for b in boxes]
@@ -176,15 +239,20 @@ def compress_payloads(boxes: Sequence[np.ndarray], keep: float, device: int = 0,
 
 
 def compress(box: Sequence[np.ndarray], components: Sequence[int], keep: float, time: int,
-             level: int, box_index: int, compressed_dir, levels: int = 1) -> List[CompressedWavelet]:
+             level: int, box_index: int, compressed_dir, levels: int = 1, pack=None) -> List[CompressedWavelet]:
     """src/compressor.cpp:192-297.  box[c] is positional; components[c] (an
     AMReX header index) only names the output file.  Writes one .xz file per
     component and returns the CompressedWavelet structs.  levels (not a
     reference parameter, default 1 = the reference's codec): see
-    compress_payloads; decompress() reads the levels from each file's header."""
+    compress_payloads; decompress() reads the levels from each file's header.
+    pack (not a reference parameter; None, 2, 3 or 4): the files hold packed
+    units (pack_payloads) through the same xz call and under the same names;
+    decompress() recognises them.  The returned structs describe the payloads
+    before packing."""
     comps = list(components)
     boxes = [box[c] for c in range(len(comps))]
     payloads = compress_payloads(boxes, keep, levels=levels)
+    written = payloads if pack is None else pack_payloads(payloads, pack)
     out = []
     for c, p in enumerate(payloads):
         cw = deserialize_compressed_wavelet(p)
@@ -196,7 +264,7 @@ def compress(box: Sequence[np.ndarray], components: Sequence[int], keep: float, 
             f = None  # a failed ofstream open silently skips the file (src/compressor.cpp:256-257)
         if f is not None:
             with f:
-                f.write(lzma.compress(p, format=lzma.FORMAT_XZ, check=XZ_CHECK, preset=xz_preset()))
+                f.write(lzma.compress(written[c], format=lzma.FORMAT_XZ, check=XZ_CHECK, preset=xz_preset()))
         out.append(cw)
     return out
 
@@ -278,7 +346,12 @@ def decompress_payloads(payloads: Sequence[bytes], device: int = 0, coarsen: int
     inside the box: it is rounded outward to multiples of 2^L (L the payload's
     levels, which must divide the box's dims), decoded from the coefficients it
     depends on alone (wc_inverse_region_host) and cropped here.  The bits are
-    those of the crop of the full decode."""
+    those of the crop of the full decode.
+
+    Packed units (compress_payloads(pack=)) are recognised by their headers and
+    unpacked first (wc_unpack_host), alone or mixed with standard payloads, on
+    every path above."""
+    payloads = _standard_payloads(payloads, device)
     dims = []
     multi = False
     for p in payloads:
@@ -289,15 +362,7 @@ def decompress_payloads(payloads: Sequence[bytes], device: int = 0, coarsen: int
     if region is not None:
         lo, hi, regions = _aligned_regions(payloads, dims, region)
     units, n, extent = capi.make_units(dims)
-    offsets = np.zeros(max(n, 1), np.uint64)
-    cur = 4
-    for i, p in enumerate(payloads):
-        offsets[i] = cur
-        cur += (len(p) + 4 + 7) // 8 * 8
-    buf = np.zeros(cur + 8, np.uint8)
-    for i, p in enumerate(payloads):
-        o = int(offsets[i])
-        buf[o:o + len(p)] = np.frombuffer(p, np.uint8)
+    buf, offsets = _laid_out(payloads)
     if region is not None:
         r = int(coarsen)
         out_units, extent = capi.region_units(units, n, regions, r)

@@ -144,6 +144,22 @@ Config parse_config_compress() {
             cfg.levels = (int)v;
         }
     }
+    std::vector<std::string> pk;  // optional, not a reference parameter
+    if (queryarr("pack", pk)) {
+        pk.erase(std::remove_if(pk.begin(), pk.end(),
+                                [](const std::string& t) { return t == "-c" || t == "-d" || t == "-estimate"; }),
+                 pk.end());
+        char* end = nullptr;
+        const long v = pk.size() == 1 ? std::strtol(pk[0].c_str(), &end, 10) : 0;
+        if (pk.size() != 1 || end == pk[0].c_str() || *end != 0 || v < 2 || v > 4) {
+            std::string given;
+            for (const std::string& t : pk) given += (given.empty() ? "" : " ") + t;
+            log_error("Bad pack (one integer, 2 to 4 value bytes): " + given);
+            cfg.pack_error = true;
+        } else {
+            cfg.pack = (int)v;
+        }
+    }
     if (!query("compresseddir", cfg.compressed_dir)) log_error("Missing compresseddir!");
     std::string preset;  // optional, not a reference parameter: no error when absent
     if (query("xzpreset", preset)) {

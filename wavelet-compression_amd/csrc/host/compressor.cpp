@@ -93,7 +93,9 @@ namespace {
 // (opt-in, xz_pool.h).
 std::vector<CompressedWavelet> write_components(const uint8_t* payload, const std::vector<uint64_t>& offsets,
                                                 const std::vector<uint32_t>& kept, const std::vector<int>& components,
-                                                int time, int level, int box_index, const std::string& compressed_dir) {
+                                                int time, int level, int box_index, const std::string& compressed_dir,
+                                                const uint8_t* packed = nullptr, const uint64_t* packed_offsets = nullptr,
+                                                const uint64_t* packed_bytes = nullptr) {
     const int n = static_cast<int>(components.size());
     std::vector<CompressedWavelet> out(n);
     const bool behind = write_behind();
@@ -103,6 +105,9 @@ std::vector<CompressedWavelet> write_components(const uint8_t* payload, const st
         CompressedWavelet cw = deserialize_compressed_wavelet(serialized);
         for (const auto& pr : cw.rle_encoded)
             if (std::fabs((double)pr.second) > INT16_MAX) cw.need32 = true;  // src/compressor.cpp:229
+        // compress_packed: the file holds the packed unit, the struct describes the payload before packing
+        if (packed)
+            serialized.assign(reinterpret_cast<const char*>(packed + packed_offsets[c]), (size_t)packed_bytes[c]);
         const std::filesystem::path fname =
             std::filesystem::path(compressed_dir) / ("compressed-wavelet-" + std::to_string(time) + "-" +
                                                      std::to_string(level) + "-" + std::to_string(components[c]) +
@@ -152,6 +157,36 @@ std::vector<CompressedWavelet> compress(multiBox3D& box, std::vector<int> compon
                                      offsets.data(), kept.data()),
           "GPU forward");
     return write_components(t_payload.get(), offsets, kept, components, time, level, box_index, compressed_dir);
+}
+
+std::vector<CompressedWavelet> wavelet_amd::compress_packed(multiBox3D& box, std::vector<int> components, double keep,
+                                                            int vbytes, int time, int level, int box_index,
+                                                            std::string compressed_dir) {
+    const int n = static_cast<int>(components.size());
+    if (n == 0) return {};
+    if (vbytes < 2 || vbytes > 4) fatal("compress_packed: " + std::to_string(vbytes) + " value bytes outside 2..4");
+    std::vector<wc_unit> units(n);
+    std::vector<const void*> cells(n);
+    for (int c = 0; c < n; ++c) {
+        const Box3D& b = box.at(c);
+        units[c] = wc_unit{0, (int32_t)b.width(), (int32_t)b.height(), (int32_t)b.depth(), 0};
+        cells[c] = b.data();
+    }
+    const uint64_t cap = wc_payload_bound(units.data(), n);
+    uint64_t pcap = 0;
+    wc_packed_bound(units.data(), n, vbytes, &pcap);
+    std::unique_ptr<uint8_t[]> payload(new uint8_t[cap]), packed(new uint8_t[pcap]);
+    std::vector<uint64_t> offsets(n + 1), poff(n + 1), pbytes(n);
+    std::vector<uint32_t> kept(n);
+    wc_ctx* ctx = thread_ctx();
+    check(ctx, wc_forward_host_units(ctx, cells.data(), WC_F32, units.data(), n, keep, payload.get(), cap, offsets.data(),
+                                     kept.data()),
+          "GPU forward");
+    check(ctx, wc_pack_host(ctx, payload.get(), offsets.data(), units.data(), n, vbytes, packed.get(), pcap, poff.data(),
+                            pbytes.data()),
+          "GPU pack");
+    return write_components(payload.get(), offsets, kept, components, time, level, box_index, compressed_dir,
+                            packed.get(), poff.data(), pbytes.data());
 }
 
 std::vector<CompressedWavelet> wavelet_amd::compress_rmse(multiBox3D& box, std::vector<int> components, int levels,

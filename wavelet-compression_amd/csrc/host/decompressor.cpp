@@ -65,6 +65,29 @@ static std::string read_file(const std::string& path) {
     return data;
 }
 
+std::string standard_payload(std::string payload) {
+    int L = 0, V = 0;
+    if (payload.size() < 20 ||
+        wc_payload_packed(reinterpret_cast<const uint8_t*>(payload.data()), 20, &L, &V) != WC_OK || V == 0)
+        return payload;  // a standard payload, or a header the decoders refuse in their own words
+    int32_t hdr[5];
+    std::memcpy(hdr, payload.data(), sizeof hdr);
+    uint64_t len = 0;
+    if (hdr[4] < 0 || wc_packed_size(reinterpret_cast<const uint8_t*>(payload.data()), payload.size(), &len) != WC_OK ||
+        len > payload.size())
+        fatal("Deserialization failed: truncated or malformed packed payload");
+    const wc_unit u{0, hdr[0], hdr[1], hdr[2], 0};
+    std::vector<uint8_t> in(payload.size() + 8);  // one unit at offset 4 (chunks 8-byte aligned)
+    std::memcpy(in.data() + 4, payload.data(), payload.size());
+    const uint64_t poff = 4;
+    std::vector<uint8_t> out(wc_payload_bound(&u, 1));
+    uint64_t off[2] = {0, 0};
+    uint32_t kept = 0;
+    wc_ctx* c = thread_ctx();
+    check(c, wc_unpack_host(c, in.data(), &poff, &u, 1, out.data(), out.size(), off, &kept), "GPU unpack");
+    return std::string(reinterpret_cast<const char*>(out.data() + off[0]), 20 + 8ull * kept);
+}
+
 }  // namespace wavelet_amd
 
 using namespace wavelet_amd;
@@ -101,7 +124,7 @@ Box3D inverse_wavelet_decompose(std::vector<float> flat, int x, int y, int z) {
 
 Box3D decompress(std::string file_path, int /*time*/, int /*level*/, int /*component*/, int /*box_idx*/) {
     flush_writes(file_path);  // this file, if compress() queued it (write-behind, opt-in), is complete first
-    const std::string payload = xz_decompress(read_file(file_path));
+    const std::string payload = standard_payload(xz_decompress(read_file(file_path)));  // a packed file unpacked
     if (payload.size() < 20) fatal("Deserialization failed: payload shorter than its header");
     int32_t hdr[5];
     std::memcpy(hdr, payload.data(), sizeof hdr);
@@ -123,7 +146,7 @@ Box3D decompress(std::string file_path, int /*time*/, int /*level*/, int /*compo
 
 Box3D wavelet_amd::decompress_coarse(const std::string& file_path, int reduce) {
     flush_writes(file_path);
-    const std::string payload = xz_decompress(read_file(file_path));
+    const std::string payload = standard_payload(xz_decompress(read_file(file_path)));  // a packed file unpacked
     if (payload.size() < 20) fatal("Deserialization failed: payload shorter than its header");
     int32_t hdr[5];
     std::memcpy(hdr, payload.data(), sizeof hdr);
@@ -149,7 +172,7 @@ Box3D wavelet_amd::decompress_coarse(const std::string& file_path, int reduce) {
 Box3D wavelet_amd::decompress_region(const std::string& file_path, std::array<int, 3> lo, std::array<int, 3> hi,
                                      int reduce) {
     flush_writes(file_path);
-    const std::string payload = xz_decompress(read_file(file_path));
+    const std::string payload = standard_payload(xz_decompress(read_file(file_path)));  // a packed file unpacked
     if (payload.size() < 20) fatal("Deserialization failed: payload shorter than its header");
     int32_t hdr[5];
     std::memcpy(hdr, payload.data(), sizeof hdr);

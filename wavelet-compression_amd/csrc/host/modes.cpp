@@ -218,6 +218,9 @@ struct Packed {
     std::vector<uint64_t> offsets;
     std::vector<uint32_t> kept;
     std::vector<double> rmse;  // round trip (estimate): calc_rmse_per_box of every unit
+    // pack=: the packed units the files hold in place of the payloads (wc_pack_host's dense layout)
+    std::unique_ptr<uint8_t[]> packed;
+    std::vector<uint64_t> packed_offsets, packed_bytes;
 };
 
 // `rmse=`: the tolerance of each component slot of a box (the units of a box
@@ -239,7 +242,11 @@ std::vector<double> slot_tolerances(const Config& cfg, const RunIndex& r) {
 // reconstruction never comes back to the host).  tol (one value per component
 // slot, or empty): the RMSE-tolerance mode in place of the keep rule.  levels >
 // 1: the multi-level mode, each unit with the levels its dimensions admit.
-Packed forward_chunk(const Chunk& c, double keep, bool round_trip, const std::vector<double>& tol, int levels) {
+// pack: 2..4 value bytes, or 0: the payloads are packed after any of the above
+// (wc_pack_host); with fewer than 4 value bytes a round trip takes its RMSE
+// from the unpacked, quantised payloads, which is what the files decode to.
+Packed forward_chunk(const Chunk& c, double keep, bool round_trip, const std::vector<double>& tol, int levels,
+                     int pack) {
     Packed p;
     const int n = (int)c.units.size();
     const uint64_t cap = wc_payload_bound(c.units.data(), n);
@@ -280,6 +287,30 @@ Packed forward_chunk(const Chunk& c, double keep, bool round_trip, const std::ve
                                    p.offsets.data(), p.kept.data()),
               "GPU forward");
     }
+    if (pack) {
+        uint64_t pcap = 0;
+        wc_packed_bound(c.units.data(), n, pack, &pcap);
+        p.packed.reset(new uint8_t[pcap]);
+        p.packed_offsets.resize(n + 1);
+        p.packed_bytes.resize(n);
+        check(ctx, wc_pack_host(ctx, p.payload.get(), p.offsets.data(), c.units.data(), n, pack, p.packed.get(), pcap,
+                                p.packed_offsets.data(), p.packed_bytes.data()),
+              "GPU pack (pack=)");
+        if (round_trip && pack < 4) {
+            std::unique_ptr<uint8_t[]> q(new uint8_t[cap]);
+            std::vector<uint64_t> qo(n + 1);
+            std::vector<uint32_t> qk(n);
+            std::vector<float> regen(std::max<uint64_t>(c.ncells, 1));
+            check(ctx, wc_unpack_host(ctx, p.packed.get(), p.packed_offsets.data(), c.units.data(), n, q.get(), cap,
+                                      qo.data(), qk.data()),
+                  "GPU unpack (pack=)");
+            // levels = NULL: each unit's L from its header (1 for a one-level payload)
+            check(ctx, wc_inverse_levels_host(ctx, q.get(), qo.data(), c.units.data(), n, nullptr, regen.data()),
+                  "GPU decompress (pack=)");
+            check(ctx, wc_rmse_host(ctx, c.cells.data(), WC_F64, regen.data(), c.units.data(), n, p.rmse.data()),
+                  "GPU RMSE (pack=)");
+        }
+    }
     return p;
 }
 
@@ -289,7 +320,43 @@ std::string unit_name(int t, int lev, int comp, int box) {
 }
 
 // Payloads -> one buffer for wc_inverse_host (offsets = 4 mod 8: pairs 8-B aligned).
-void inverse_batch(const std::vector<std::string>& payloads, const std::vector<wc_unit>& units, float* out) {
+// Files written with pack= are recognised by their headers and unpacked first, all of a batch in one call.
+void unpack_batch(std::vector<std::string>& payloads, const std::vector<wc_unit>& units) {
+    std::vector<size_t> which;
+    std::vector<wc_unit> pu;
+    std::vector<uint64_t> offs;
+    uint64_t cur = 4;
+    for (size_t i = 0; i < payloads.size(); ++i) {
+        const std::string& p = payloads[i];
+        int L = 0, V = 0;
+        if (p.size() < 20 || wc_payload_packed(reinterpret_cast<const uint8_t*>(p.data()), 20, &L, &V) != WC_OK || V == 0)
+            continue;  // a standard payload, or a header the decoder refuses in its own words
+        uint64_t len = 0;
+        if (wc_packed_size(reinterpret_cast<const uint8_t*>(p.data()), p.size(), &len) != WC_OK || len > p.size())
+            fatal("Deserialization failed: truncated or malformed packed payload");
+        which.push_back(i);
+        pu.push_back(units[i]);
+        offs.push_back(cur);
+        cur += (p.size() + 7) / 8 * 8;
+    }
+    if (which.empty()) return;
+    std::vector<uint8_t> buf(cur + 8, 0);
+    for (size_t k = 0; k < which.size(); ++k)
+        std::memcpy(buf.data() + offs[k], payloads[which[k]].data(), payloads[which[k]].size());
+    const int n = (int)which.size();
+    const uint64_t cap = wc_payload_bound(pu.data(), n);
+    std::unique_ptr<uint8_t[]> out(new uint8_t[cap]);
+    std::vector<uint64_t> oo(n + 1);
+    std::vector<uint32_t> kept(n);
+    wc_ctx* ctx = thread_ctx();
+    check(ctx, wc_unpack_host(ctx, buf.data(), offs.data(), pu.data(), n, out.get(), cap, oo.data(), kept.data()),
+          "GPU unpack");
+    for (int k = 0; k < n; ++k)
+        payloads[which[k]].assign(reinterpret_cast<const char*>(out.get() + oo[k]), 20 + 8ull * kept[k]);
+}
+
+void inverse_batch(std::vector<std::string>& payloads, const std::vector<wc_unit>& units, float* out) {
+    unpack_batch(payloads, units);
     std::vector<uint64_t> offs(payloads.size());
     uint64_t cur = 4;
     for (size_t i = 0; i < payloads.size(); ++i) {
@@ -339,7 +406,7 @@ uint64_t run_cells(const RunIndex& r, size_t nc) {
 template <class OnChunk>
 void compress_run(const RunIndex& r, double keep, const std::filesystem::path& dir, OnChunk on_chunk,
                   const std::vector<int>& devs, bool round_trip = false, const std::vector<double>& tol = {},
-                  int levels = 1) {
+                  int levels = 1, int pack = 0) {
     const size_t nc = r.comp_idxs.size();
     std::vector<Chunk> chunks = plan_chunks(r, nc, chunk_cells(run_cells(r, nc), devs.size()));
     auto jobs_of = [&](const Chunk& c, const Packed& p) {
@@ -348,8 +415,11 @@ void compress_run(const RunIndex& r, double keep, const std::filesystem::path& d
             for (size_t k = 0; k < nc; ++k) {
                 const size_t u = i * nc + k;
                 const BoxRef& b = c.boxes[i];
-                jobs.push_back(XzJob{p.payload.get() + p.offsets[u], 20 + 8ull * p.kept[u],
-                                     (dir / unit_name(b.t, b.lev, r.comp_idxs[k], b.box)).string()});
+                const std::string name = (dir / unit_name(b.t, b.lev, r.comp_idxs[k], b.box)).string();
+                if (p.packed)
+                    jobs.push_back(XzJob{p.packed.get() + p.packed_offsets[u], p.packed_bytes[u], name});
+                else
+                    jobs.push_back(XzJob{p.payload.get() + p.offsets[u], 20 + 8ull * p.kept[u], name});
             }
         return jobs;
     };
@@ -360,7 +430,7 @@ void compress_run(const RunIndex& r, double keep, const std::filesystem::path& d
         for (size_t i = next.fetch_add(1); i < chunks.size(); i = next.fetch_add(1)) {
             Chunk& c = chunks[i];
             load_chunk(r, c, threads);
-            auto p = std::make_shared<Packed>(forward_chunk(c, keep, round_trip, tol, levels));
+            auto p = std::make_shared<Packed>(forward_chunk(c, keep, round_trip, tol, levels, pack));
             std::vector<XzJob> jobs = jobs_of(c, *p);
             if (xz_done.valid()) xz_done.get();
             xz_done = std::async(std::launch::async,
@@ -384,8 +454,17 @@ static int levels_of_run(const Config& cfg) {
     return cfg.levels;
 }
 
+// `pack=`: logged as levels= is.
+static int pack_of_run(const Config& cfg) {
+    if (cfg.pack)
+        log_info("pack=" + std::to_string(cfg.pack) + " given: every payload is stored packed, its values in " +
+                 std::to_string(cfg.pack) + " bytes (not a reference parameter; the reference cannot decode these "
+                 "files)");
+    return cfg.pack;
+}
+
 int compress(const Config& cfg) {
-    if (cfg.rmse_error || cfg.levels_error) return 1;
+    if (cfg.rmse_error || cfg.levels_error || cfg.pack_error) return 1;
     if (cfg.xz_preset >= 0) set_xz_preset((uint32_t)cfg.xz_preset);
     if (xz_preset() != 6) log_info("xz preset " + std::to_string(xz_preset() & 0xff) +
                                    ((xz_preset() & 0x80000000u) ? "e" : "") + " (the reference's is 6)");
@@ -413,7 +492,7 @@ int compress(const Config& cfg) {
     const auto t1 = Clock::now();
     compress_run(r, (double)cfg.keep, std::filesystem::path(cfg.compressed_dir),
                  [](size_t, const Chunk&, const Packed&) {}, run_devices(), false, slot_tolerances(cfg, r),
-                 levels_of_run(cfg));
+                 levels_of_run(cfg), pack_of_run(cfg));
     log_info("Compression completed in " + fmt_double(since(t1)) + " seconds.");
     return 0;
 }
@@ -488,7 +567,7 @@ int decompress(const Config& cfg) {
 }
 
 int estimate(Config& cfg) {
-    if (cfg.rmse_error || cfg.levels_error) return 1;
+    if (cfg.rmse_error || cfg.levels_error || cfg.pack_error) return 1;
     const int num_components = (int)cfg.components.size();
     TempDir scratch;
     const std::vector<std::string> files = format_files(cfg.data_dir, cfg.min_time, cfg.min_time);
@@ -527,7 +606,7 @@ int estimate(Config& cfg) {
             maxv[k] = std::max(maxv[k], hi[k]);
         }
         chunk_rmse[ci] = p.rmse;
-    }, run_devices(), /*round_trip=*/true, slot_tolerances(cfg, r), levels_of_run(cfg));
+    }, run_devices(), /*round_trip=*/true, slot_tolerances(cfg, r), levels_of_run(cfg), pack_of_run(cfg));
     for (const auto& [ci, rm] : chunk_rmse)
         for (size_t u = 0; u < rm.size(); ++u) all_rmses[u % nc].push_back(rm[u]);
     // The reference reads every file back (src/modes.cpp:250-265) and exits on

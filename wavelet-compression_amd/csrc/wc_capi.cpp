@@ -9,7 +9,8 @@
 // host-only wc_tol_threshold: wc_tolhost.cpp; wc_forward_levels_tol_host:
 // wc_leveltolhost.cpp; the host-only wc_tol_levels_threshold: wc_leveltolrule.cpp;
 // wc_forward_levels_budget_host: wc_budgethost.cpp; the host-only wc_budget_select
-// and wc_budget_thresholds: wc_budgetrule.cpp).
+// and wc_budget_thresholds: wc_budgetrule.cpp; wc_pack, wc_unpack and their _host
+// forms: wc_packhost.cpp; the packed format's host-only rule: wc_packrule.cpp).
 //
 // Forward path per batch (wc_forward), every unit shape: K1 k_transform{,_fast}
 // -> flat coefficients in HBM scratch (sparse staging: only the flagged
@@ -423,7 +424,8 @@ void wc_ctx_destroy(wc_ctx* c) {
                       &c->plan.d_edesc, &c->plan.d_ixtiles, &c->plan.d_rtiles,
                       &c->plan.d_rdtiles, &c->rowinfo,    &c->istate,        &c->npairs,
                       &c->tol_in,        &c->tol_bins,       &c->h_thresh,       &c->h_bound,
-                      &c->lv_side};
+                      &c->lv_side,       &c->pk_desc,        &c->pk_in,          &c->pk_out,
+                      &c->pk_off,        &c->pk_bytes};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (Plan& P : c->plan_cache) free_plan(P);

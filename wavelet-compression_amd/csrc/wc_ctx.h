@@ -27,6 +27,10 @@
 //                    selection rule on one unit's final array (plain C++, linked
 //                    alone by tests/cpp/test_budget.cpp), the argument checks
 //                    and wc_forward_levels_budget_host
+//   wc_packrule.cpp / wc_packhost.cpp  packed payloads: the format's host rule
+//                    (plain C++, linked alone with wc_packfmt.h by
+//                    tests/cpp/test_pack.cpp), and wc_pack, wc_unpack and their
+//                    _host forms
 //   wc_coarsehost.cpp host side of the reduced-resolution inverse: wc_coarse_units,
 //                    the argument checks and wc_inverse_coarse_host
 //   wc_regionrule.cpp / wc_regionhost.cpp  the sub-box inverse: wc_region_align
@@ -116,6 +120,14 @@ hipError_t launch_corner_box(hipStream_t, const CornerDesc*, const FTile* ftiles
 hipError_t launch_decode_region(hipStream_t, const RegionDesc*, const FTile* dtiles, uint32_t ndt,
                                 const uint8_t* payload, const uint64_t* offsets, uint32_t* ticket,
                                 unsigned long long* status, float* compact, uint32_t* err, int ordered, uint32_t* bad);
+
+// wc_pack.hip: the packed payload format's transcoders (k_pack_widths + k_pack_body, k_unpack)
+hipError_t launch_pack_units(hipStream_t, const PackDesc*, const FTile* tiles, uint32_t ntiles, const uint8_t* payload,
+                             const uint64_t* offsets, int vbytes, int n, uint8_t* packed, uint64_t* packed_offsets,
+                             uint64_t* packed_bytes, uint32_t* err);
+hipError_t launch_unpack_units(hipStream_t, const PackDesc*, const FTile* tiles, uint32_t ntiles, const uint8_t* packed,
+                               const uint64_t* packed_offsets, uint64_t cap, int n, uint8_t* payload, uint64_t* offsets,
+                               uint32_t* kept, uint32_t* err);
 
 struct DevBuf {
     void* p = nullptr;
@@ -234,6 +246,14 @@ struct wc_ctx {
     // of the level passes (coef_extent / 8 floats); the call's levels and work
     // lists go through the same pinned block and tol_in
     wc::DevBuf lv_side;
+    // packed payloads (wc_pack / wc_unpack): the batch's descriptors and tiles
+    // (PackDesc[n] | FTile[ntiles]) stay on the device while the units and the
+    // value bytes recur (pk_key, pk_vbytes); the _host forms' staging
+    wc::DevBuf pk_desc;
+    std::vector<wc_unit> pk_key;
+    int pk_vbytes = 0;
+    uint32_t pk_ntiles = 0;
+    wc::DevBuf pk_in, pk_out, pk_off, pk_bytes;
     std::unique_ptr<wc::HostPool> hpool;
     // uploads from pageable host memory: copied by upool's threads into pinned
     // bounce slots, each slot's copy to the device ordered by an event

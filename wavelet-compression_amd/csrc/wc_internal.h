@@ -146,6 +146,20 @@ struct BudgetState {
 };
 static_assert(sizeof(BudgetState) == 16, "one 16-B load");
 
+// One unit of the packed-payload transcoders (wc_pack.hip): the box, the unit's
+// slot in the packed buffer (wc_packed_bound's scheme) and its slot in the
+// standard payload buffer (wc_payload_bound's).  Kept on the device while a
+// batch recurs.
+struct PackDesc {
+    uint64_t pk_off;   // packed slot: prefix of pad8(S(cells) + 4), == 4 (mod 8)
+    uint64_t pay_off;  // forward slot: prefix of 24 + 8 * cells, == 4 (mod 8)
+    int32_t W, H, D;
+    uint32_t ncells;
+};
+static_assert(sizeof(PackDesc) == 32, "descriptor of 8-B members first");
+constexpr int kPackTile = 2048;                        // pairs per transcoder workgroup (wc_pack.hip has the arithmetic)
+constexpr uint64_t kPackMaxCells = uint64_t(1) << 21;  // the device transcoders' largest unit (WC_PACK_MAX_CELLS)
+
 // Per-unit skip words (bad[u]) that k_decode<true> and k_decode_corner leave for
 // the launches after them: the level passes and k_inverse{,_fast}<true> skip a
 // unit unless its word is kUnitRun.
