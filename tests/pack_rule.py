@@ -1,7 +1,9 @@
 """numpy restatement of the packed payload format and of its value rule q
 (include/wavelet_amd.h, "Opt-in packed payloads").  TEST INFRASTRUCTURE ONLY:
-the yardstick of tests/test_pack_cpu.py and tests/test_gpu_pack.py; the product
-never imports it.
+the yardstick of tests/test_pack_cpu.py, tests/test_gpu_pack.py and
+tests/test_gpu_pack_fuzz.py; the product never imports it.  pack() and unpack()
+loop over chunks in plain numpy: about 1.6 s and 1.5 s for the 2^21 pairs of
+limit_unit(), which the tests restate once, at one V.
 
 A standard payload is 20 bytes of header (int32 W, H, D, ncoeff, nrle) and nrle
 pairs {int32 run, fp32 value}.  A packed unit: the header with ncoeff replaced by
@@ -216,3 +218,125 @@ def batch(src="f32"):
         big = O.narrow(big.astype(np.float64) * (1.0 + 2.0 ** -30))
     units.append(("64^3", LR.payload(big, 1, keep=0.999)[0], True))
     return units
+
+
+# ------------------------------------------------------------- the fuzz units --
+# Units for the transcoders alone, made with standard() as crafted() makes its
+# own: the runs need not fit the box, so no decoder reads them (finite = False).
+FUZZ_DIMS = [(1, 1, 1), (2, 2, 2), (3, 5, 7), (5, 1, 9), (6, 10, 14), (33, 17, 9), (0, 4, 4), (8, 8, 8), (16, 16, 16),
+             (24, 8, 40), (64, 32, 16)]
+FULL_DIMS = [(2, 2, 2), (3, 5, 7), (8, 8, 8), (6, 10, 14)]  # cells 8, 105, 512, 840: 105 % 8 and 840 % 64 are not 0
+FUZZ_SEEDS = (0, 1, 2)
+FUZZ_DRAWN = 40
+MANY_DIMS = [(2, 2, 2), (1, 1, 1), (0, 4, 4), (3, 5, 7), (4, 4, 4), (8, 8, 8)]
+LIMIT_DIMS = (128, 128, 128)  # WC_PACK_MAX_CELLS = 2^21 cells
+
+
+def levels_allowed(W, H, D):
+    """The L a header of this box may carry: 1, and every L <= 4 whose 2^L divides each dimension."""
+    return [L for L in range(1, MAX_LEVELS + 1) if L == 1 or (W | H | D) & ((1 << L) - 1) == 0]
+
+
+def chunk_widths(pay):
+    """-> (the width of every chunk, the pairs in the last chunk) of a standard payload."""
+    runs = parse(pay)[4]
+    nch = (len(runs) + 63) // 64
+    w = [int(np.bitwise_or.reduce(runs[64 * c:64 * c + 64])).bit_length() for c in range(nch)]
+    return w, (len(runs) - 64 * (nch - 1) if nch else 0)
+
+
+def runs_of_widths(rng, n, widths):
+    """n runs whose chunk c has the width widths[c] exactly: every run below 2^w, one of them with bit w - 1 set."""
+    runs = np.zeros(n, np.uint32)
+    for c, w in enumerate(widths):
+        m = min(64, n - 64 * c)
+        if w:
+            r = rng.integers(0, 1 << int(w), m, dtype=np.uint64)
+            r[rng.integers(0, m)] |= np.uint64(1) << np.uint64(int(w) - 1)
+            runs[64 * c:64 * c + m] = r.astype(np.uint32)
+    return runs
+
+
+def value_bits(rng, n, share=0.25):
+    """n uniform uint32 bit patterns, `share` of them from SPECIALS."""
+    bits = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+    pick = rng.random(n) < share
+    bits[pick] = SPECIALS[rng.integers(0, SPECIALS.size, int(pick.sum()))]
+    return bits
+
+
+class _Deck:
+    """The widths 0..31 dealt without replacement and reshuffled when none is left: 63 draws hold every width."""
+
+    def __init__(self, rng):
+        self.rng, self.left = rng, []
+
+    def draw(self):
+        if not self.left:
+            self.left = self.rng.permutation(32).tolist()
+        return self.left.pop()
+
+
+def pair_count(rng, cells, cls):
+    """A pair count of class cls (0..15; 10 and above: uniform), clipped to the cell count."""
+    k64, k2048 = int(rng.integers(1, max(cells // 64, 1) + 1)), int(rng.integers(1, max(cells // TILE, 1) + 1))
+    n = [0, 1, cells, cells - 1, 64 * k64 - 1, 64 * k64, 64 * k64 + 1, TILE * k2048 - 1, TILE * k2048, TILE * k2048 + 1,
+         int(rng.integers(0, cells + 1))][min(cls, 10)]
+    return min(max(n, 0), cells)
+
+
+def fuzz_batch(seed):
+    """-> FUZZ_DRAWN + len(FULL_DIMS) units (what, payload, False).  The drawn
+    ones: dimensions from FUZZ_DIMS (each at least three times), L from
+    levels_allowed, a pair count of one of eleven classes (pair_count; the unit
+    index walks them, the uniform one six times in sixteen), per chunk a width from a deck of 0..31 (one deck for
+    the full chunks, one for the short last chunks) or, one time in eight, an
+    all-zero chunk; value bits uniform with a quarter from SPECIALS.  Then the full
+    slots: n = cells and every width 31 on FULL_DIMS."""
+    rng = np.random.default_rng(9300 + seed)
+    full, last = _Deck(rng), _Deck(rng)
+    order = [FUZZ_DIMS[i % len(FUZZ_DIMS)] for i in rng.permutation(FUZZ_DRAWN)]
+    units = []
+    for i, (W, H, D) in enumerate(order):
+        cells = W * H * D
+        allowed = levels_allowed(W, H, D)
+        L = allowed[int(rng.integers(0, len(allowed)))]
+        n = pair_count(rng, cells, (i + 5 * seed) % 16)
+        nch = (n + 63) // 64
+        widths = [0 if rng.random() < 0.125 else full.draw() for _ in range(nch)]
+        if n % 64:
+            widths[-1] = last.draw()
+        units.append((f"s{seed}u{i}:{W}x{H}x{D}/L{L}/n{n}",
+                      standard(W, H, D, L, runs_of_widths(rng, n, widths), value_bits(rng, n)), False))
+    for W, H, D in FULL_DIMS:
+        n = W * H * D
+        units.append((f"s{seed}full:{W}x{H}x{D}", standard(W, H, D, 1, runs_of_widths(rng, n, [31] * ((n + 63) // 64)),
+                                                          value_bits(rng, n)), False))
+    return units
+
+
+def many_units(count):
+    """-> `count` tiny units (what, payload, False), each list a prefix of the
+    longer ones: dimensions cycling over MANY_DIMS, n uniform in 0..cells (so the
+    lengths vary; the units without cells and the draws of n = 0 are bare 20-byte
+    headers), widths uniform in 0..12."""
+    rng = np.random.default_rng(9400)
+    units = []
+    for i in range(count):
+        W, H, D = MANY_DIMS[i % len(MANY_DIMS)]
+        n = int(rng.integers(0, W * H * D + 1))
+        widths = rng.integers(0, 13, (n + 63) // 64)
+        units.append((f"m{i}:{W}x{H}x{D}/n{n}", standard(W, H, D, 1, runs_of_widths(rng, n, widths), value_bits(rng, n)),
+                      False))
+    return units
+
+
+def limit_unit(n):
+    """-> one unit (what, payload, False) of 128^3 cells (WC_PACK_MAX_CELLS) at L = 1
+    with n pairs: runs below 2^12, one chunk in sixteen all zero, value bits uniform."""
+    rng = np.random.default_rng(9500 + n % 9973)
+    W, H, D = LIMIT_DIMS
+    runs = rng.integers(0, 1 << 12, n, dtype=np.uint64).astype(np.uint32)
+    zero = np.repeat(rng.random((n + 63) // 64) < 1.0 / 16, 64)[:n]
+    runs[zero] = 0
+    return (f"limit/n{n}", standard(W, H, D, 1, runs, rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)), False)

@@ -33,7 +33,7 @@ class Batch:
     """Payloads in the forward's slot layout, with the restatement's packed units
     and quantised payloads per V (computed once, left unchanged)."""
 
-    def __init__(self, wc, units):
+    def __init__(self, wc, units, vs=VS, restated=None):
         self.what = [u[0] for u in units]
         self.pays = [u[1] for u in units]
         self.n = len(self.pays)
@@ -42,9 +42,16 @@ class Batch:
         self.units, _, self.extent = wc.capi.make_units(self.dims)
         self.pay_off, self.pay_cap = PR.payload_slots(self.dims)
         self.buf = self.layout(self.pays, self.pay_off, self.pay_cap)
-        self.packed = {V: [PR.pack(p, V) for p in self.pays] for V in VS}
-        self.quant = {V: [PR.quantise(p, V) for p in self.pays] for V in VS}
-        self.slots = {V: PR.slot_offsets(self.dims, V) for V in VS}
+        packed, quant = restated or ({V: [PR.pack(p, V) for p in self.pays] for V in vs},
+                                     {V: [PR.quantise(p, V) for p in self.pays] for V in vs})
+        self.packed, self.quant = packed, quant
+        self.slots = {V: PR.slot_offsets(self.dims, V) for V in vs}
+
+    def head(self, wc, k):
+        """The first k units as a batch of their own; the restatement's bytes are shared, not computed again."""
+        units = list(zip(self.what[:k], self.pays[:k]))
+        return Batch(wc, units, vs=tuple(self.packed), restated=({V: p[:k] for V, p in self.packed.items()},
+                                                                 {V: q[:k] for V, q in self.quant.items()}))
 
     @staticmethod
     def layout(items, offs, cap, margin=64):

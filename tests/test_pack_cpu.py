@@ -103,6 +103,99 @@ def test_host_rule_equals_restatement(wc, units):
             assert e.value.code == C.WC_ERR_FORMAT
 
 
+@pytest.fixture(scope="module")
+def fuzz():
+    """The units tests/test_gpu_pack_fuzz.py transcodes on the GPU, over its seeds."""
+    return [u for seed in PR.FUZZ_SEEDS for u in PR.fuzz_batch(seed)]
+
+
+def test_fuzz_generators_reach_the_classes(fuzz):
+    """The GPU inputs have the power claimed for them.  A generator change that
+    loses a class fails here, on the CPU."""
+    full, last, residues, counts, values = set(), set(), set(), set(), set()
+    zero_beside = False
+    for what, pay, _ in fuzz:
+        W, H, D, L, runs, bits = PR.parse(pay)
+        cells, n = W * H * D, len(runs)
+        assert L in PR.levels_allowed(W, H, D) and n <= cells, what
+        w, m = PR.chunk_widths(pay)
+        assert w == list(PR.pack(pay, 2)[20:20 + len(w)]), what
+        full.update(w[:-1] if m < 64 else w)
+        if 0 < m < 64:
+            last.add(w[-1])
+        if w:
+            residues.add(m % 8)
+        zero_beside = zero_beside or any((a == 0) != (b == 0) for a, b in zip(w, w[1:]))
+        counts.update(k for k, hit in (("0", n == 0 and cells > 0), ("1", n == 1), ("cells", n == cells > 0),
+                                       ("cells-1", n == cells - 1 > 0), ("64k-1", n % 64 == 63),
+                                       ("64k", n and n % 64 == 0), ("64k+1", n > 64 and n % 64 == 1),
+                                       ("tile-1", n % PR.TILE == PR.TILE - 1), ("tile", n and n % PR.TILE == 0),
+                                       ("tile+1", n > PR.TILE and n % PR.TILE == 1), ("no cells", cells == 0),
+                                       ("cells%8", n == cells and cells % 8), ("cells%64", n == cells and cells % 64),
+                                       ("tiles>2", n > 2 * PR.TILE)) if hit)
+        values.update(bits.tolist())
+    assert full == set(range(32)), sorted(set(range(32)) - full)
+    assert last == set(range(32)), sorted(set(range(32)) - last)
+    assert residues == set(range(8)) and zero_beside
+    assert counts == {"0", "1", "cells", "cells-1", "64k-1", "64k", "64k+1", "tile-1", "tile", "tile+1", "no cells",
+                      "cells%8", "cells%64", "tiles>2"}, counts
+    assert set(PR.SPECIALS.tolist()) <= values
+    assert {tuple(int(v) for v in np.frombuffer(p[:12], np.int32)) for _, p, _ in fuzz} == set(PR.FUZZ_DIMS)
+    # the full slots: S(N) with no slack, at every V, on cell counts that are no multiple of 8 or of 64
+    fulls = [(w, p) for w, p, _ in fuzz if "full" in w]
+    assert len(fulls) == len(PR.FUZZ_SEEDS) * len(PR.FULL_DIMS)
+    for what, pay in fulls:
+        W, H, D = (int(v) for v in np.frombuffer(pay[:12], np.int32))
+        for V in VS:
+            assert len(PR.pack(pay, V)) == PR.worst(W * H * D, V), (what, V)
+    assert {int(np.prod(d)) % 8 != 0 for d in PR.FULL_DIMS} == {True, False}
+    assert any(int(np.prod(d)) % 64 and not int(np.prod(d)) % 8 for d in PR.FULL_DIMS)
+
+
+def test_many_units_and_limit_unit_generators():
+    many = PR.many_units(2100)
+    assert [w for w, _, _ in PR.many_units(65)] == [w for w, _, _ in many[:65]]
+    assert all(a[1] == b[1] for a, b in zip(PR.many_units(65), many))  # a prefix: the GPU test slices one list
+    lens = {len(PR.pack(p, 3)) for _, p, _ in many}
+    assert 20 in lens and len(lens) > 100
+    assert {tuple(int(v) for v in np.frombuffer(p[:12], np.int32)) for _, p, _ in many} == set(PR.MANY_DIMS)
+    # the device limit: 2^21 cells, all kept; widths up to 12 and scattered all-zero chunks
+    what, pay, _ = PR.limit_unit(2 ** 21)
+    W, H, D, L, runs, bits = PR.parse(pay)
+    assert W * H * D == len(runs) == 2 ** 21 and L == 1 and int(runs.max()) < 1 << 12
+    per = runs.reshape(-1, 64).max(axis=1)
+    assert 0 < int((per == 0).sum()) < per.size // 8 and int(per.max()) >= 1 << 11
+    assert len(PR.parse(PR.limit_unit(100)[1])[4]) == 100
+
+
+def test_host_rule_equals_restatement_on_the_fuzz(wc, fuzz):
+    """As test_host_rule_equals_restatement, on the fuzz units and on the prefix of
+    the many-units list that holds every one of its dimensions several times."""
+    C = wc.capi
+    for what, pay, _ in fuzz + PR.many_units(130):
+        W, H, D, L, runs, bits = PR.parse(pay)
+        for V in VS:
+            want = PR.pack(pay, V)
+            got = C.pack_unit(pay, V)
+            assert got == want, (what, V)
+            assert C.packed_size(got) == len(got) == PR.packed_size(want), (what, V)
+            assert len(got) <= PR.worst(W * H * D, V), (what, V)
+            assert C.payload_packed(got) == (L, V), (what, V)
+            back = C.unpack_unit(got)
+            assert back == PR.unpack(want) == PR.quantise(pay, V), (what, V)
+            assert C.pack_unit(back, V) == got, (what, V)
+
+
+def test_host_rule_on_the_limit_unit(wc):
+    """The 2^21-cell unit at V = 3, the one case the GPU test runs it at."""
+    C = wc.capi
+    what, pay, _ = PR.limit_unit(2 ** 21)
+    want = PR.pack(pay, 3)
+    got = C.pack_unit(pay, 3)
+    assert got == want and C.packed_size(got) == len(got) == PR.packed_size(want)
+    assert C.unpack_unit(got) == PR.quantise(pay, 3)
+
+
 def test_slots_and_bound(wc):
     dims = [(8, 8, 8), (0, 4, 4), (32, 16, 8), (3, 5, 7), (64, 64, 64)]
     units, n, _ = wc.capi.make_units(dims)
@@ -136,6 +229,12 @@ def test_host_rule_refusals(wc):
     odd = PR.standard(6, 8, 8, 1, np.zeros(1, np.uint32), np.zeros(1, np.uint32))
     odd = odd[:12] + np.array([-2], np.int32).tobytes() + odd[16:]
     assert code(C.pack_unit, odd, 3) == C.WC_ERR_FORMAT  # 4 does not divide 6
+    # dimensions whose product wraps in 64 bits (2^30 * 2^30 * 16 = 2^64) are no unit without cells
+    for t in (0, -2, -49):
+        wrap = np.array([1 << 30, 1 << 30, 16, t, 0], np.int32).tobytes()
+        assert code(C.payload_packed, wrap) == C.WC_ERR_FORMAT, t
+        assert code(C.pack_unit, wrap, 3) == C.WC_ERR_FORMAT and code(C.unpack_unit, wrap) == C.WC_ERR_FORMAT, t
+    assert C.payload_packed(np.array([1 << 30, 1 << 30, 0, -49, 0], np.int32).tobytes()) == (1, 3)  # no cells
     good = C.pack_unit(pay, 3)
     assert code(C.unpack_unit, pay) == C.WC_ERR_FORMAT  # a standard payload is not a packed unit
     assert code(C.unpack_unit, good[:-1]) == C.WC_ERR_INVALID

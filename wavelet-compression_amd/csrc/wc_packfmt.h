@@ -37,7 +37,9 @@ WC_PACK_HD uint32_t pack_value(uint32_t b, int vbytes) {
 // every dimension, as wc_payload_levels asks.
 WC_PACK_HD bool pack_header(int32_t W, int32_t H, int32_t D, int32_t tag, int& L, int& V) {
     if (W < 0 || H < 0 || D < 0) return false;
-    const uint64_t cells = (uint64_t)W * (uint64_t)H * (uint64_t)D;
+    const uint64_t wh = (uint64_t)W * (uint64_t)H;  // below 2^62; three factors could wrap (2^30 * 2^30 * 16 = 2^64)
+    if (D && wh > 0x7FFFFFFFull) return false;
+    const uint64_t cells = wh * (uint64_t)D;
     if (cells > 0x7FFFFFFFull) return false;
     if (tag >= 0) {
         L = 1;
