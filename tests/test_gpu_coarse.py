@@ -223,6 +223,30 @@ def test_lookback_forms_give_the_same_cells(wc, ctx, fast, small):
         ctx.set_option(WC_OPT_SPIN_LIMIT, 0)
 
 
+def test_odd_direct_partial_empty_and_multi_tile_units_in_one_batch(wc, ctx, fast):
+    """One batch of the decode kernel's whole-box form under each look-back form:
+    an odd unit at L = 1, r = 0 (the region map is not stated for it), a unit
+    with r = L, one with 0 < r < L, one without cells, and a unit of the `fast`
+    batch whose payload spans more than two pair tiles."""
+    mix = [((5, 6, 7), 1, 0), ((16, 16, 16), 2, 2), ((16, 8, 24), 3, 2), ((0, 4, 4), 1, 1)]
+    pays = [R.payload(field(i % 3, W, H, D, seed=80 + i) if W * H * D else np.zeros((D, H, W), np.float32), L,
+                      keep=0.99)[0] for i, ((W, H, D), L, _) in enumerate(mix)]
+    assert fast.dims[2] == (64, 64, 64) and int(np.frombuffer(fast.pays[2][16:20], "<i4")[0]) > 2 * 4096
+    case = Case(wc, pays + [fast.pays[2]], [r for _, _, r in mix] + [1])
+    assert case.levels == [1, 2, 3, 1, 3]
+    dev = Dev(case)
+    for what, opt, val, back in (("ordered", None, 0, 0), ("tickets", WC_OPT_ORDERED, 0, 1),
+                                 ("reversed", WC_OPT_REVERSE_TILES, 1, 0)):
+        if opt is not None:
+            ctx.set_option(opt, val)
+        try:
+            dev.refill()
+            case.check(run_device(ctx, case, dev), what=what)
+        finally:
+            if opt is not None:
+                ctx.set_option(opt, back)
+
+
 def test_host_form_in_several_runs(wc, ctx, fast, small):
     want = {id(c): run_device(ctx, c) for c in (fast, small[0.99])}
     ctx.set_option(WC_OPT_HOST_CHUNK, 3000)

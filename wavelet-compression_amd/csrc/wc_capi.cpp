@@ -10,7 +10,11 @@
 // wc_leveltolhost.cpp; the host-only wc_tol_levels_threshold: wc_leveltolrule.cpp;
 // wc_forward_levels_budget_host: wc_budgethost.cpp; the host-only wc_budget_select
 // and wc_budget_thresholds: wc_budgetrule.cpp; wc_pack, wc_unpack and their _host
-// forms: wc_packhost.cpp; the packed format's host-only rule: wc_packrule.cpp).
+// forms: wc_packhost.cpp; the packed format's host-only rule: wc_packrule.cpp;
+// wc_forward_levels_host and wc_inverse_levels_host: wc_levelshost.cpp;
+// wc_inverse_coarse_host and wc_coarse_units: wc_coarsehost.cpp;
+// wc_inverse_region_host and the driver it shares with wc_inverse_coarse_host:
+// wc_regionhost.cpp; wc_region_align and wc_region_units: wc_regionrule.cpp).
 //
 // Forward path per batch (wc_forward), every unit shape: K1 k_transform{,_fast}
 // -> flat coefficients in HBM scratch (sparse staging: only the flagged
@@ -374,6 +378,63 @@ bool single_level(const int32_t* levels, int n) {
     return true;
 }
 
+// What wc_forward_levels, _tol and _budget begin with, in the order that decides
+// which error a caller sees first: units, dtype, n == 0, null buffers (own_ok:
+// the mode's own buffers are there), the mode's `validate`, the capacity, the
+// alignments (`more`: the mode's own outputs), then the device, the plan and
+// the scratch.  *run = false: the call ends here with the value returned (an
+// error, or WC_OK for n == 0).
+struct AlignedArg {
+    const void* p;
+    const char* what;
+    uintptr_t align;
+};
+template <class Validate>
+int forward_levels_begin(wc_ctx* c, const void* d_cells, int dtype, const wc_unit* units, int n, const void* d_payload,
+                         uint64_t cap, const void* d_offsets, const void* d_kept, bool own_ok, Validate validate,
+                         std::initializer_list<AlignedArg> more, bool* run) {
+    *run = false;
+    if (!c) return WC_ERR_INVALID;
+    int rc;
+    if ((rc = validate_units(c, units, n))) return rc;
+    if (dtype != WC_F32 && dtype != WC_F64) return fail(c, WC_ERR_INVALID, "dtype");
+    if (n == 0) return WC_OK;
+    if (!d_cells || !d_payload || !d_offsets || !d_kept || !own_ok) return fail(c, WC_ERR_INVALID, "null buffer");
+    if ((rc = validate())) return rc;
+    if (cap < wc_payload_bound(units, n)) return fail(c, WC_ERR_INVALID, "payload_capacity < wc_payload_bound");
+    if ((rc = check_aligned(c, d_cells, "cells")) || (rc = check_aligned(c, d_payload, "payload")) ||
+        (rc = check_aligned(c, d_offsets, "offsets", 8)) || (rc = check_aligned(c, d_kept, "kept", 4)))
+        return rc;
+    for (const AlignedArg& a : more)
+        if ((rc = check_aligned(c, a.p, a.what, a.align))) return rc;
+    if ((rc = set_device(c)) || (rc = get_plan(c, units, n)) || (rc = ensure_scratch(c))) return rc;
+    *run = true;
+    return WC_OK;
+}
+
+// ... and end with: ncoeff = -L into the headers of the units with L >= 2.
+int patch_level_headers(wc_ctx* c, const LevelWork& w, uint8_t* d_payload) {
+    StageTimer t(c, WC_STAGE_LEVELS);
+    hipError_t e = launch_level_headers(c->stream, (const UnitDev*)c->plan.d_units.p, w.hdr, w.nhdr, d_payload);
+    return e == hipSuccess ? WC_OK : hip_fail(c, e, "level header launch");
+}
+
+// wc_forward_emit and _tol after their argument checks: these units' plan must
+// be the one whose coefficients are staged (staged: as the mode needs them);
+// then the per-unit tile tickets (tdone) and the look-back status words, which
+// are per call: everything after the unit keys is zeroed.
+int restage(wc_ctx* c, const wc_unit* units, int n, bool staged, const char* who) {
+    const uint64_t gen = c->plan_gen;
+    int rc;
+    if ((rc = set_device(c)) || (rc = get_plan(c, units, n))) return rc;
+    // get_plan keeps the cached plan (and so the staged scratch) only for the same units
+    if (!staged || gen != c->plan_gen)
+        return fail(c, WC_ERR_INVALID, std::string(who) + ": no staged coefficients for these units (wc_forward_stage)");
+    const size_t st_off = 16 + 8ull * n;
+    hipError_t e = hipMemsetAsync((uint8_t*)c->state.p + st_off, 0, c->plan.state_bytes - st_off, c->stream);
+    return e == hipSuccess ? WC_OK : hip_fail(c, e, "memset status");
+}
+
 }  // namespace
 
 extern "C" {
@@ -694,18 +755,7 @@ int wc_forward_emit(wc_ctx* c, const wc_unit* units, int n, double keep, const f
     if ((rc = check_aligned(c, d_payload, "payload")) || (rc = check_aligned(c, d_offsets, "offsets", 8)) ||
         (rc = check_aligned(c, d_kept, "kept", 4)))
         return rc;
-    const bool staged = c->staged;
-    const uint64_t gen = c->plan_gen;
-    if ((rc = set_device(c)) || (rc = get_plan(c, units, n))) return rc;
-    // get_plan keeps the cached plan (and so the staged scratch) only for the same units
-    if (!staged || gen != c->plan_gen)
-        return fail(c, WC_ERR_INVALID, "wc_forward_emit: no staged coefficients for these units (wc_forward_stage)");
-    // per-unit tile tickets (tdone) and look-back status words are per call:
-    // zero everything after the unit keys
-    const Plan& P = c->plan;
-    const size_t st_off = 16 + 8ull * n;
-    hipError_t e = hipMemsetAsync((uint8_t*)c->state.p + st_off, 0, P.state_bytes - st_off, c->stream);
-    if (e != hipSuccess) return hip_fail(c, e, "memset status");
+    if ((rc = restage(c, units, n, c->staged, "wc_forward_emit"))) return rc;
     if ((rc = stage_emit(c, n, keep, thresh, d_payload, d_offsets, d_kept))) return rc;
     c->staged = true;  // the coefficients are still there: emit again with another threshold
     return WC_OK;
@@ -748,17 +798,8 @@ int wc_forward_emit_tol(wc_ctx* c, const wc_unit* units, int n, const double* to
         (rc = check_aligned(c, d_kept, "kept", 4)) || (rc = check_aligned(c, d_thresh, "thresh", 4)) ||
         (rc = check_aligned(c, d_bound, "bound", 8)))
         return rc;
-    const bool staged = c->staged && !c->sparse_staged;  // every coefficient is needed
-    const uint64_t gen = c->plan_gen;
-    if ((rc = set_device(c)) || (rc = get_plan(c, units, n))) return rc;
-    if (!staged || gen != c->plan_gen)
-        return fail(c, WC_ERR_INVALID,
-                    "wc_forward_emit_tol: no staged coefficients for these units (wc_forward_stage)");
-    // tickets and look-back status words are per call (wc_forward_emit)
-    const Plan& P = c->plan;
-    const size_t st_off = 16 + 8ull * n;
-    hipError_t e = hipMemsetAsync((uint8_t*)c->state.p + st_off, 0, P.state_bytes - st_off, c->stream);
-    if (e != hipSuccess) return hip_fail(c, e, "memset status");
+    // every coefficient is needed
+    if ((rc = restage(c, units, n, c->staged && !c->sparse_staged, "wc_forward_emit_tol"))) return rc;
     const float* uth = nullptr;
     if ((rc = stage_tol(c, n, tol, d_thresh, d_bound, &uth)) ||
         (rc = stage_emit(c, n, 0.0, nullptr, d_payload, d_offsets, d_kept, nullptr, uth)))
@@ -905,6 +946,108 @@ int inverse_impl(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets,
     return rc;
 }
 
+// What wc_inverse_coarse and wc_inverse_region fill alike of a unit's descriptor
+// (f: the full-size unit, o: its derived unit).  The origin and end stay 0, and
+// with them a unit without cells: no tile reads more than the end of such a unit.
+void compact_desc(RegionDesc& d, const wc_unit& f, const wc_unit& o, int L, int r) {
+    d = RegionDesc{};
+    d.L = (uint32_t)(L - r);
+    d.direct = r == L ? 1u : 0u;
+    d.out_off = o.cell_offset;
+    d.W = f.nx;
+    d.H = f.ny;
+    d.D = f.nz;
+    const uint64_t cells = (uint64_t)f.nx * f.ny * f.nz;
+    d.want = L >= 2 ? -L : (int32_t)cells;
+    if (!cells) return;
+    d.w = (uint32_t)(f.nx >> r);
+    d.h = (uint32_t)(f.ny >> r);
+    d.d = (uint32_t)(f.nz >> r);
+    d.sx = (uint32_t)o.nx;
+    d.sy = (uint32_t)o.ny;
+    d.sz = (uint32_t)o.nz;
+    d.dmagic = rows_magic(f.nz);
+    d.hmagic = rows_magic(f.ny);
+}
+
+// The reduced-resolution and the sub-box inverse, from the units' descriptors
+// (dst_off and dt_begin are filled here, from the plans).  Two plans: the one of
+// the full-size units gives the pair tiles of the decode and their look-back
+// granules; the one of out_units (the derived units: the regions' extents >> r,
+// with `whole` the boxes >> r) places each compact unit in the coefficient
+// scratch and runs the remaining L - r levels and the one-level inverse on it,
+// as wc_inverse_levels does on full arrays.  Both are dense plans
+// (WC_OPT_INVERSE_ROWS = 0) and stay in the plan cache.
+int inverse_compact(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                    const wc_unit* out_units, float* d_out, std::vector<RegionDesc>& desc, bool whole) {
+    int rc;
+    if ((rc = check_aligned(c, d_payload, "payload")) || (rc = check_aligned(c, d_offsets, "offsets", 8)) ||
+        (rc = check_aligned(c, d_out, "out")))
+        return rc;
+    if ((rc = set_device(c))) return rc;
+    std::vector<int32_t> rest(n);  // levels of the compact unit: L - r (1 for r == L, which runs nothing)
+    bool any_direct = false, any_run = false;
+    uint32_t maxt = 0;  // the batch's largest ceil(end / kFlatTile): no tile index at or past it has work
+    for (int u = 0; u < n; ++u) {
+        const RegionDesc& d = desc[u];
+        rest[u] = std::max<int32_t>(1, (int32_t)d.L);
+        if (!d.end) continue;  // a unit or a region without cells
+        maxt = std::max(maxt, (d.end - 1) / (uint32_t)kFlatTile + 1);
+        any_direct |= d.direct != 0;
+        any_run |= d.direct == 0;
+    }
+    // the full units' plan: the decoder ignores their cell offsets, so the key carries none
+    std::vector<wc_unit> full(units, units + n);
+    for (wc_unit& u : full) u.cell_offset = 0;
+    const bool rows = c->opt_inv_rows;
+    c->opt_inv_rows = false;  // the plans' key holds it (wc_inverse_levels)
+    const FTile* dtiles = nullptr;
+    uint32_t ndt = 0;
+    size_t dstate = 0;
+    if ((rc = get_plan(c, full.data(), n)) == WC_OK) {
+        const Plan& F = c->plan;
+        dtiles = (const FTile*)F.d_dtiles.p;  // the plan moves into the cache below: its buffers stay
+        dstate = decode_state_bytes(F);
+        // dtiles is ordered by tile index, then unit: the tiles below maxt are a prefix of it
+        for (int u = 0; u < n; ++u) {
+            desc[u].dt_begin = F.units[u].dt_begin;
+            ndt += std::min(F.units[u].ndt, maxt);
+        }
+        rc = get_plan(c, out_units, n);
+    }
+    c->opt_inv_rows = rows;
+    if (rc || (rc = ensure_scratch(c)) || (rc = ensure(c, c->state, dstate))) return rc;
+    const Plan& P = c->plan;
+    for (int u = 0; u < n; ++u) desc[u].dst_off = P.units[u].coef_off;
+    LevelWork w;
+    const void* d_desc = nullptr;
+    if ((rc = upload_levels(c, n, rest.data(), &w, desc.data(), sizeof(RegionDesc) * n, &d_desc))) return rc;
+    DecodeState ds;
+    hipError_t e = decode_state(c, n, dstate, true, &ds);
+    if (e != hipSuccess) return hip_fail(c, e, "memset");
+    uint32_t* bad = (uint32_t*)c->npairs.p;  // per-unit "skip" words, as in wc_inverse_levels
+    {
+        StageTimer t(c, WC_STAGE_DECODE);
+        // the compact units: positions without a pair must read as zeros
+        if (P.coef_extent && (e = hipMemsetAsync(c->coef.p, 0, sizeof(float) * P.coef_extent, c->stream)) != hipSuccess)
+            return hip_fail(c, e, "memset");
+        e = launch_decode_region(c->stream, (const RegionDesc*)d_desc, dtiles, ndt, d_payload, d_offsets, ds.ticket,
+                                 ds.status, (float*)c->coef.p, (uint32_t*)c->errflag.p, ds.ordered, bad, whole);
+        // the units with r == L: their compact units are their cells
+        if (e == hipSuccess && any_direct)
+            e = launch_corner_box(c->stream, (const RegionDesc*)d_desc, (const FTile*)P.d_ftiles.p,
+                                  (uint32_t)P.ftiles.size(), (const float*)c->coef.p, d_out, bad);
+        if (e != hipSuccess) return hip_fail(c, e, "compact decode launch");
+    }
+    c->err_check_pending = true;  // malformed payloads surface at the next wc_synchronize
+    if (w.maxl >= 2 && (rc = run_levels(c, w, false, false, bad))) return rc;
+    if (!any_run) return WC_OK;  // every compact unit was its result, or no region had cells
+    StageTimer t(c, WC_STAGE_INVERSE);
+    e = launch_inverse(c->stream, (const float*)c->coef.p, 0, (const UnitDev*)P.d_units.p, (const XTile*)P.d_ixtiles.p,
+                       P.ign, P.lds_inverse, P.ifast, P.lds_fast, d_out, bad);
+    return e == hipSuccess ? WC_OK : hip_fail(c, e, "inverse launch");
+}
+
 }  // namespace
 
 extern "C" {
@@ -973,19 +1116,10 @@ int wc_inverse_flat(wc_ctx* c, const float* d_flat, const wc_unit* units, int n,
 int wc_forward_levels(wc_ctx* c, const void* d_cells, int dtype, const wc_unit* units, int n, const int32_t* levels,
                       double keep, const float* thresh, uint8_t* d_payload, uint64_t cap, uint64_t* d_offsets,
                       uint32_t* d_kept) {
-    if (!c) return WC_ERR_INVALID;
-    int rc;
-    if ((rc = validate_units(c, units, n))) return rc;
-    if (dtype != WC_F32 && dtype != WC_F64) return fail(c, WC_ERR_INVALID, "dtype");
-    if (n == 0) return WC_OK;
-    if (!d_cells || !d_payload || !d_offsets || !d_kept) return fail(c, WC_ERR_INVALID, "null buffer");
-    if ((rc = validate_levels(c, units, n, levels))) return rc;
-    if (cap < wc_payload_bound(units, n)) return fail(c, WC_ERR_INVALID, "payload_capacity < wc_payload_bound");
-    if ((rc = check_aligned(c, d_cells, "cells")) || (rc = check_aligned(c, d_payload, "payload")) ||
-        (rc = check_aligned(c, d_offsets, "offsets", 8)) || (rc = check_aligned(c, d_kept, "kept", 4)))
-        return rc;
-    if ((rc = set_device(c)) || (rc = get_plan(c, units, n))) return rc;
-    if ((rc = ensure_scratch(c))) return rc;
+    bool run;
+    int rc = forward_levels_begin(c, d_cells, dtype, units, n, d_payload, cap, d_offsets, d_kept, true,
+                                  [&] { return validate_levels(c, units, n, levels); }, {}, &run);
+    if (!run) return rc;
     if (single_level(levels, n) && !thresh)  // wc_forward itself
         return forward_staged(c, d_cells, dtype, n, keep, d_payload, d_offsets, d_kept);
     LevelWork w;
@@ -993,9 +1127,7 @@ int wc_forward_levels(wc_ctx* c, const void* d_cells, int dtype, const wc_unit* 
     if ((rc = upload_levels(c, n, levels, &w)) || (rc = stage_transform(c, d_cells, dtype, 0.0, false)) ||
         (rc = run_levels(c, w, true, !thresh)) || (rc = stage_emit(c, n, keep, thresh, d_payload, d_offsets, d_kept)))
         return rc;
-    StageTimer t(c, WC_STAGE_LEVELS);
-    hipError_t e = launch_level_headers(c->stream, (const UnitDev*)c->plan.d_units.p, w.hdr, w.nhdr, d_payload);
-    return e == hipSuccess ? WC_OK : hip_fail(c, e, "level header launch");
+    return patch_level_headers(c, w, d_payload);
 }
 
 // Multi-level forward with per-unit RMSE tolerances: wc_forward_levels' staging
@@ -1005,21 +1137,15 @@ int wc_forward_levels(wc_ctx* c, const void* d_cells, int dtype, const wc_unit* 
 int wc_forward_levels_tol(wc_ctx* c, const void* d_cells, int dtype, const wc_unit* units, int n,
                           const int32_t* levels, const double* tol, uint8_t* d_payload, uint64_t cap,
                           uint64_t* d_offsets, uint32_t* d_kept, float* d_thresh, double* d_bound) {
-    if (!c) return WC_ERR_INVALID;
-    int rc;
-    if ((rc = validate_units(c, units, n))) return rc;
-    if (dtype != WC_F32 && dtype != WC_F64) return fail(c, WC_ERR_INVALID, "dtype");
-    if (n == 0) return WC_OK;
-    if (!d_cells || !d_payload || !d_offsets || !d_kept) return fail(c, WC_ERR_INVALID, "null buffer");
-    // an odd dimension passes validate_levels only at L = 1, where validate_tol refuses it
-    if ((rc = validate_levels(c, units, n, levels)) || (rc = validate_tol(c, units, n, tol))) return rc;
-    if (cap < wc_payload_bound(units, n)) return fail(c, WC_ERR_INVALID, "payload_capacity < wc_payload_bound");
-    if ((rc = check_aligned(c, d_cells, "cells")) || (rc = check_aligned(c, d_payload, "payload")) ||
-        (rc = check_aligned(c, d_offsets, "offsets", 8)) || (rc = check_aligned(c, d_kept, "kept", 4)) ||
-        (rc = check_aligned(c, d_thresh, "thresh", 4)) || (rc = check_aligned(c, d_bound, "bound", 8)))
-        return rc;
-    if ((rc = set_device(c)) || (rc = get_plan(c, units, n))) return rc;
-    if ((rc = ensure_scratch(c))) return rc;
+    bool run;
+    int rc = forward_levels_begin(
+        c, d_cells, dtype, units, n, d_payload, cap, d_offsets, d_kept, true,
+        [&] {  // an odd dimension passes validate_levels only at L = 1, where validate_tol refuses it
+            const int v = validate_levels(c, units, n, levels);
+            return v ? v : validate_tol(c, units, n, tol);
+        },
+        {{d_thresh, "thresh", 4}, {d_bound, "bound", 8}}, &run);
+    if (!run) return rc;
     LevelWork w;
     LevelTolWork t;
     build_leveltol(c, n, levels, tol, !d_thresh, &t);
@@ -1030,9 +1156,7 @@ int wc_forward_levels_tol(wc_ctx* c, const void* d_cells, int dtype, const wc_un
         (rc = stage_leveltol(c, n, w.maxl, t, (const uint8_t*)d_blob, d_thresh, d_bound)) ||
         (rc = stage_emit(c, n, 0.0, &zero, d_payload, d_offsets, d_kept)))
         return rc;
-    StageTimer timer(c, WC_STAGE_LEVELS);
-    hipError_t e = launch_level_headers(c->stream, (const UnitDev*)c->plan.d_units.p, w.hdr, w.nhdr, d_payload);
-    return e == hipSuccess ? WC_OK : hip_fail(c, e, "level header launch");
+    return patch_level_headers(c, w, d_payload);
 }
 
 // Multi-level forward under a pair budget per unit: wc_forward_levels' staging
@@ -1042,25 +1166,19 @@ int wc_forward_levels_tol(wc_ctx* c, const void* d_cells, int dtype, const wc_un
 int wc_forward_levels_budget(wc_ctx* c, const void* d_cells, int dtype, const wc_unit* units, int n,
                              const int32_t* levels, const uint32_t* max_pairs, uint8_t* d_payload, uint64_t cap,
                              uint64_t* d_offsets, uint32_t* d_kept, float* d_thresh, uint32_t* d_key) {
-    if (!c) return WC_ERR_INVALID;
-    int rc;
-    if ((rc = validate_units(c, units, n))) return rc;
-    if (dtype != WC_F32 && dtype != WC_F64) return fail(c, WC_ERR_INVALID, "dtype");
-    if (n == 0) return WC_OK;
-    if (!d_cells || !d_payload || !d_offsets || !d_kept || !max_pairs) return fail(c, WC_ERR_INVALID, "null buffer");
     std::vector<int32_t> ones;
-    if (!levels) {
-        ones.assign(n, 1);
-        levels = ones.data();
-    }
-    if ((rc = validate_budget(c, units, n, levels))) return rc;
-    if (cap < wc_payload_bound(units, n)) return fail(c, WC_ERR_INVALID, "payload_capacity < wc_payload_bound");
-    if ((rc = check_aligned(c, d_cells, "cells")) || (rc = check_aligned(c, d_payload, "payload")) ||
-        (rc = check_aligned(c, d_offsets, "offsets", 8)) || (rc = check_aligned(c, d_kept, "kept", 4)) ||
-        (rc = check_aligned(c, d_thresh, "thresh", 4)) || (rc = check_aligned(c, d_key, "key", 4)))
-        return rc;
-    if ((rc = set_device(c)) || (rc = get_plan(c, units, n))) return rc;
-    if ((rc = ensure_scratch(c))) return rc;
+    bool run;
+    int rc = forward_levels_begin(
+        c, d_cells, dtype, units, n, d_payload, cap, d_offsets, d_kept, max_pairs != nullptr,
+        [&] {
+            if (!levels) {
+                ones.assign(n, 1);
+                levels = ones.data();
+            }
+            return validate_budget(c, units, n, levels);
+        },
+        {{d_thresh, "thresh", 4}, {d_key, "key", 4}}, &run);
+    if (!run) return rc;
     LevelWork w;
     LevelTolWork t;
     build_leveltol(c, n, levels, nullptr, !d_thresh, &t, sizeof(uint32_t), sizeof(BudgetState));
@@ -1072,9 +1190,7 @@ int wc_forward_levels_budget(wc_ctx* c, const void* d_cells, int dtype, const wc
         (rc = stage_budget(c, n, w.maxl, t, (const uint8_t*)d_blob, d_thresh, d_key)) ||
         (rc = stage_emit(c, n, 0.0, &zero, d_payload, d_offsets, d_kept)))
         return rc;
-    StageTimer timer(c, WC_STAGE_LEVELS);
-    hipError_t e = launch_level_headers(c->stream, (const UnitDev*)c->plan.d_units.p, w.hdr, w.nhdr, d_payload);
-    return e == hipSuccess ? WC_OK : hip_fail(c, e, "level header launch");
+    return patch_level_headers(c, w, d_payload);
 }
 
 int wc_decompose_levels(wc_ctx* c, const void* d_cells, int dtype, const wc_unit* units, int n, const int32_t* levels,
@@ -1174,12 +1290,8 @@ int wc_inverse_levels(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_off
     return e == hipSuccess ? WC_OK : hip_fail(c, e, "inverse launch");
 }
 
-// Reduced-resolution inverse (wc_coarse.hip).  Two plans: the one of the
-// full-size units gives the pair tiles of the corner decode and their look-back
-// granules; the one of out_units (the derived units (W, H, D) >> r) places each
-// compact corner in the coefficient scratch and runs the remaining L - r levels
-// and the one-level inverse on it, as wc_inverse_levels does on full arrays.
-// Both are dense plans (WC_OPT_INVERSE_ROWS = 0) and stay in the plan cache.
+// Reduced-resolution inverse: every unit's region is its whole primed box
+// (inverse_compact, wc_region.hip).
 int wc_inverse_coarse(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
                       const int32_t* levels, const int32_t* reduce, const wc_unit* out_units, float* d_out) {
     if (!c) return WC_ERR_INVALID;
@@ -1196,101 +1308,18 @@ int wc_inverse_coarse(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_off
         return rc;
     if (std::all_of(reduce, reduce + n, [](int32_t r) { return r == 0; }))
         return wc_inverse_levels(c, d_payload, d_offsets, out_units, n, levels, d_out);
-    if ((rc = check_aligned(c, d_payload, "payload")) || (rc = check_aligned(c, d_offsets, "offsets", 8)) ||
-        (rc = check_aligned(c, d_out, "out")))
-        return rc;
-    if ((rc = set_device(c))) return rc;
-    // the full units' plan: the decoder ignores their cell offsets, so the key carries none
-    std::vector<wc_unit> full(units, units + n);
-    for (wc_unit& u : full) u.cell_offset = 0;
-    const bool rows = c->opt_inv_rows;
-    c->opt_inv_rows = false;  // the plans' key holds it (wc_inverse_levels)
-    const FTile* dtiles = nullptr;
-    uint32_t ndt = 0;
-    size_t dstate = 0;
-    std::vector<CornerDesc> desc(n);
-    bool any_direct = false, any_run = false;
-    uint32_t maxt = 0;  // the batch's largest ceil(end / kFlatTile): no tile index at or past it has work
+    std::vector<RegionDesc>& desc = c->cdesc;
+    desc.resize(n);
     for (int u = 0; u < n; ++u) {
-        const wc_unit& f = units[u];
-        const wc_unit& o = out_units[u];
-        if (!((uint64_t)f.nx * f.ny * f.nz)) continue;  // no tile reads the descriptor's end
-        desc[u].end = (uint32_t)((((uint64_t)o.nx - 1) * f.ny + ((uint64_t)o.ny - 1)) * f.nz + o.nz);
-        maxt = std::max(maxt, (desc[u].end - 1) / (uint32_t)kFlatTile + 1);
+        RegionDesc& d = desc[u];
+        compact_desc(d, units[u], out_units[u], levels[u], reduce[u]);
+        // valid for odd dimensions (L = 1, r = 0), which region_end is not; 0 for a unit without cells
+        if (d.W && d.H && d.D) d.end = (uint32_t)((((uint64_t)d.w - 1) * d.H + ((uint64_t)d.h - 1)) * d.D + d.d);
     }
-    if ((rc = get_plan(c, full.data(), n)) == WC_OK) {
-        const Plan& F = c->plan;
-        dtiles = (const FTile*)F.d_dtiles.p;  // the plan moves into the cache below: its buffers stay
-        dstate = decode_state_bytes(F);
-        // dtiles is ordered by tile index, then unit: the tiles below maxt are a prefix of it
-        for (int u = 0; u < n; ++u) {
-            desc[u].dt_begin = F.units[u].dt_begin;
-            ndt += std::min(F.units[u].ndt, maxt);
-        }
-        rc = get_plan(c, out_units, n);
-    }
-    c->opt_inv_rows = rows;
-    if (rc || (rc = ensure_scratch(c)) || (rc = ensure(c, c->state, dstate))) return rc;
-    const Plan& P = c->plan;
-    std::vector<int32_t> rest(n);  // levels left after the corner: L - r (1 for r == L, which runs nothing)
-    for (int u = 0; u < n; ++u) {
-        const wc_unit& f = units[u];
-        const wc_unit& o = out_units[u];
-        CornerDesc& d = desc[u];
-        const int L = levels[u], r = reduce[u];
-        rest[u] = std::max(1, L - r);
-        d.direct = r == L ? 1u : 0u;
-        d.dst_off = P.units[u].coef_off;
-        d.out_off = o.cell_offset;
-        d.W = f.nx;
-        d.H = f.ny;
-        d.D = f.nz;
-        d.w = (uint32_t)o.nx;
-        d.h = (uint32_t)o.ny;
-        d.d = (uint32_t)o.nz;
-        const uint64_t cells = (uint64_t)f.nx * f.ny * f.nz;
-        d.want = L >= 2 ? -L : (int32_t)cells;
-        if (!cells) continue;  // no tile reads the descriptor
-        d.dmagic = rows_magic(f.nz);
-        d.hmagic = rows_magic(f.ny);
-        any_direct |= d.direct != 0;
-        any_run |= d.direct == 0;
-    }
-    LevelWork w;
-    const void* d_desc = nullptr;
-    if ((rc = upload_levels(c, n, rest.data(), &w, desc.data(), sizeof(CornerDesc) * n, &d_desc))) return rc;
-    DecodeState ds;
-    hipError_t e = decode_state(c, n, dstate, true, &ds);
-    if (e != hipSuccess) return hip_fail(c, e, "memset");
-    uint32_t* bad = (uint32_t*)c->npairs.p;  // per-unit "skip" words, as in wc_inverse_levels
-    {
-        StageTimer t(c, WC_STAGE_DECODE);
-        // the compact corners: positions without a pair must read as zeros
-        if (P.coef_extent && (e = hipMemsetAsync(c->coef.p, 0, sizeof(float) * P.coef_extent, c->stream)) != hipSuccess)
-            return hip_fail(c, e, "memset");
-        e = launch_decode_corner(c->stream, (const CornerDesc*)d_desc, dtiles, ndt, d_payload, d_offsets, ds.ticket,
-                                 ds.status, (float*)c->coef.p, (uint32_t*)c->errflag.p, ds.ordered, bad);
-        // the units with r == L: their corners are their cells
-        if (e == hipSuccess && any_direct)
-            e = launch_corner_box(c->stream, (const CornerDesc*)d_desc, (const FTile*)P.d_ftiles.p,
-                                  (uint32_t)P.ftiles.size(), (const float*)c->coef.p, d_out, bad);
-        if (e != hipSuccess) return hip_fail(c, e, "corner decode launch");
-    }
-    c->err_check_pending = true;  // malformed payloads surface at the next wc_synchronize
-    if (w.maxl >= 2 && (rc = run_levels(c, w, false, false, bad))) return rc;
-    if (!any_run) return WC_OK;  // every unit's corner was its result
-    StageTimer t(c, WC_STAGE_INVERSE);
-    e = launch_inverse(c->stream, (const float*)c->coef.p, 0, (const UnitDev*)P.d_units.p, (const XTile*)P.d_ixtiles.p,
-                       P.ign, P.lds_inverse, P.ifast, P.lds_fast, d_out, bad);
-    return e == hipSuccess ? WC_OK : hip_fail(c, e, "inverse launch");
+    return inverse_compact(c, d_payload, d_offsets, units, n, out_units, d_out, desc, true);
 }
 
-// Sub-box inverse (wc_region.hip).  The two plans of wc_inverse_coarse: the one
-// of the full-size units gives the pair tiles of the region decode and their
-// look-back granules; the one of out_units (the derived units: the regions'
-// extents >> r) places each compact unit in the coefficient scratch and runs the
-// L - r levels and the one-level inverse on it.  Both are dense plans
-// (WC_OPT_INVERSE_ROWS = 0) and stay in the plan cache.
+// Sub-box inverse (inverse_compact, wc_region.hip).
 int wc_inverse_region(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
                       const int32_t* levels, const int32_t* reduce, const wc_region* regions, const wc_unit* out_units,
                       float* d_out) {
@@ -1311,117 +1340,21 @@ int wc_inverse_region(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_off
     if ((rc = validate_levels(c, units, n, levels)) ||
         (rc = validate_region(c, units, n, levels, reduce, regions, out_units)))
         return rc;
-    if ((rc = check_aligned(c, d_payload, "payload")) || (rc = check_aligned(c, d_offsets, "offsets", 8)) ||
-        (rc = check_aligned(c, d_out, "out")))
-        return rc;
-    if ((rc = set_device(c))) return rc;
-    // the full units' plan: the decoder ignores their cell offsets, so the key carries none
-    std::vector<wc_unit> full(units, units + n);
-    for (wc_unit& u : full) u.cell_offset = 0;
-    std::vector<RegionDesc> desc(n);
-    std::vector<int32_t> rest(n);  // levels of the compact unit: L - r (1 for r == L, which runs nothing)
-    bool any_direct = false, any_run = false;
-    uint32_t maxt = 0;  // the batch's largest ceil(end / kFlatTile): no tile index at or past it has work
+    std::vector<RegionDesc>& desc = c->cdesc;
+    desc.resize(n);
     for (int u = 0; u < n; ++u) {
-        const wc_unit& f = units[u];
-        const wc_unit& o = out_units[u];
-        const wc_region& g = regions[u];
         RegionDesc& d = desc[u];
-        const int L = levels[u], r = reduce[u];
-        std::memset(&d, 0, sizeof d);  // end = 0: no tile reads the rest
-        rest[u] = std::max(1, L - r);
-        d.direct = r == L ? 1u : 0u;
-        d.out_off = o.cell_offset;
-        d.W = f.nx;
-        d.H = f.ny;
-        d.D = f.nz;
-        const uint64_t cells = (uint64_t)f.nx * f.ny * f.nz;
-        d.want = L >= 2 ? -L : (int32_t)cells;
-        if (!cells) continue;
-        d.w = (uint32_t)(f.nx >> r);
-        d.h = (uint32_t)(f.ny >> r);
-        d.d = (uint32_t)(f.nz >> r);
-        d.L = (uint32_t)(L - r);
+        compact_desc(d, units[u], out_units[u], levels[u], reduce[u]);
+        if (!(d.W && d.H && d.D)) continue;  // end = 0
+        const wc_region& g = regions[u];
+        const int r = reduce[u];
         d.ox = (uint32_t)(g.x0 >> r);
         d.oy = (uint32_t)(g.y0 >> r);
         d.oz = (uint32_t)(g.z0 >> r);
-        d.sx = (uint32_t)o.nx;
-        d.sy = (uint32_t)o.ny;
-        d.sz = (uint32_t)o.nz;
-        d.dmagic = rows_magic(f.nz);
-        d.hmagic = rows_magic(f.ny);
-        d.end = (uint32_t)region_end(d.w, d.h, d.d, d.L, d.ox, d.oy, d.oz, d.sx, d.sy, d.sz, (uint32_t)f.ny,
-                                     (uint32_t)f.nz);  // <= W*H*D < 2^31
-        if (!d.end) continue;  // a region without cells
-        maxt = std::max(maxt, (d.end - 1) / (uint32_t)kFlatTile + 1);
-        any_direct |= d.direct != 0;
-        any_run |= d.direct == 0;
+        d.end = (uint32_t)region_end(d.w, d.h, d.d, d.L, d.ox, d.oy, d.oz, d.sx, d.sy, d.sz, (uint32_t)d.H,
+                                     (uint32_t)d.D);  // <= W*H*D < 2^31; 0: a region without cells
     }
-    const bool rows = c->opt_inv_rows;
-    c->opt_inv_rows = false;  // the plans' key holds it (wc_inverse_levels)
-    const FTile* dtiles = nullptr;
-    uint32_t ndt = 0;
-    size_t dstate = 0;
-    if ((rc = get_plan(c, full.data(), n)) == WC_OK) {
-        const Plan& F = c->plan;
-        dtiles = (const FTile*)F.d_dtiles.p;  // the plan moves into the cache below: its buffers stay
-        dstate = decode_state_bytes(F);
-        // dtiles is ordered by tile index, then unit: the tiles below maxt are a prefix of it
-        for (int u = 0; u < n; ++u) {
-            desc[u].dt_begin = F.units[u].dt_begin;
-            ndt += std::min(F.units[u].ndt, maxt);
-        }
-        rc = get_plan(c, out_units, n);
-    }
-    c->opt_inv_rows = rows;
-    if (rc || (rc = ensure_scratch(c)) || (rc = ensure(c, c->state, dstate))) return rc;
-    const Plan& P = c->plan;
-    // the descriptors, then (for k_corner_box) the CornerDesc of every unit: its corner is the compact unit
-    std::vector<uint8_t> blob(sizeof(RegionDesc) * n + (any_direct ? sizeof(CornerDesc) * n : 0));
-    for (int u = 0; u < n; ++u) desc[u].dst_off = P.units[u].coef_off;
-    std::memcpy(blob.data(), desc.data(), sizeof(RegionDesc) * n);
-    if (any_direct) {
-        std::vector<CornerDesc> cd(n);
-        for (int u = 0; u < n; ++u) {
-            std::memset(&cd[u], 0, sizeof(CornerDesc));
-            cd[u].dst_off = desc[u].dst_off;
-            cd[u].out_off = desc[u].out_off;
-            cd[u].w = desc[u].sx;
-            cd[u].h = desc[u].sy;
-            cd[u].d = desc[u].sz;
-            cd[u].direct = desc[u].direct;
-        }
-        std::memcpy(blob.data() + sizeof(RegionDesc) * n, cd.data(), sizeof(CornerDesc) * n);
-    }
-    LevelWork w;
-    const void* d_desc = nullptr;
-    if ((rc = upload_levels(c, n, rest.data(), &w, blob.data(), blob.size(), &d_desc))) return rc;
-    DecodeState ds;
-    hipError_t e = decode_state(c, n, dstate, true, &ds);
-    if (e != hipSuccess) return hip_fail(c, e, "memset");
-    uint32_t* bad = (uint32_t*)c->npairs.p;  // per-unit "skip" words, as in wc_inverse_levels
-    {
-        StageTimer t(c, WC_STAGE_DECODE);
-        // the compact units: positions without a pair must read as zeros
-        if (P.coef_extent && (e = hipMemsetAsync(c->coef.p, 0, sizeof(float) * P.coef_extent, c->stream)) != hipSuccess)
-            return hip_fail(c, e, "memset");
-        e = launch_decode_region(c->stream, (const RegionDesc*)d_desc, dtiles, ndt, d_payload, d_offsets, ds.ticket,
-                                 ds.status, (float*)c->coef.p, (uint32_t*)c->errflag.p, ds.ordered, bad);
-        // the units with r == L: their compact units are their cells
-        if (e == hipSuccess && any_direct)
-            e = launch_corner_box(c->stream,
-                                  (const CornerDesc*)((const uint8_t*)d_desc + sizeof(RegionDesc) * n),
-                                  (const FTile*)P.d_ftiles.p, (uint32_t)P.ftiles.size(), (const float*)c->coef.p,
-                                  d_out, bad);
-        if (e != hipSuccess) return hip_fail(c, e, "region decode launch");
-    }
-    c->err_check_pending = true;  // malformed payloads surface at the next wc_synchronize
-    if (w.maxl >= 2 && (rc = run_levels(c, w, false, false, bad))) return rc;
-    if (!any_run) return WC_OK;  // every compact unit was its result, or no region had cells
-    StageTimer t(c, WC_STAGE_INVERSE);
-    e = launch_inverse(c->stream, (const float*)c->coef.p, 0, (const UnitDev*)P.d_units.p, (const XTile*)P.d_ixtiles.p,
-                       P.ign, P.lds_inverse, P.ifast, P.lds_fast, d_out, bad);
-    return e == hipSuccess ? WC_OK : hip_fail(c, e, "inverse launch");
+    return inverse_compact(c, d_payload, d_offsets, units, n, out_units, d_out, desc, false);
 }
 
 int wc_rmse(wc_ctx* c, const void* d_orig, int dtype, const float* d_regen, const wc_unit* units, int n,

@@ -32,11 +32,13 @@
 //                    tests/cpp/test_pack.cpp), and wc_pack, wc_unpack and their
 //                    _host forms
 //   wc_coarsehost.cpp host side of the reduced-resolution inverse: wc_coarse_units,
-//                    the argument checks and wc_inverse_coarse_host
+//                    the argument checks and wc_inverse_coarse_host (a call of
+//                    wc_regionhost.cpp's driver)
 //   wc_regionrule.cpp / wc_regionhost.cpp  the sub-box inverse: wc_region_align
 //                    and wc_region_units (plain C++, linked alone with
 //                    wc_regionmap.h by tests/cpp/test_regionrule.cpp), the
-//                    argument checks and wc_inverse_region_host
+//                    argument checks, wc_inverse_region_host and the host driver
+//                    of both modes
 #pragma once
 
 #include "wavelet_amd.h"
@@ -107,19 +109,16 @@ hipError_t launch_leveltol_mask(hipStream_t, const UnitDev*, const LtUnit*, cons
 hipError_t launch_budget(hipStream_t, const UnitDev*, int, const LtUnit*, const uint32_t* max_pairs, const uint2* items,
                          uint32_t nitems, uint32_t chunk, const uint32_t* split_units, uint32_t nsplit, int maxl,
                          const float* coef, uint32_t* gbins, BudgetState* state, float* thresh, uint32_t* key);
-// wc_coarse.hip: the corner decode (over a prefix of the full plan's decode
-// tiles) into the compact corners, and the copy of the corners of the units with
-// r == L to their Box3D cells (over the derived plan's flat tiles)
-hipError_t launch_decode_corner(hipStream_t, const CornerDesc*, const FTile* dtiles, uint32_t ndt,
-                                const uint8_t* payload, const uint64_t* offsets, uint32_t* ticket,
-                                unsigned long long* status, float* corner, uint32_t* err, int ordered, uint32_t* bad);
-hipError_t launch_corner_box(hipStream_t, const CornerDesc*, const FTile* ftiles, uint32_t nft, const float* corner,
-                             float* out, const uint32_t* bad);
-// wc_region.hip: the region decode (over a prefix of the full plan's decode
-// tiles) into the compact units of the sub-box inverse
+// wc_region.hip: the decode of the reduced-resolution and the sub-box inverse
+// (over a prefix of the full plan's decode tiles) into the compact units (whole:
+// every region is its whole primed box, wc_inverse_coarse), and the copy of the
+// compact units with r == L to their Box3D cells (over the derived plan's flat tiles)
 hipError_t launch_decode_region(hipStream_t, const RegionDesc*, const FTile* dtiles, uint32_t ndt,
                                 const uint8_t* payload, const uint64_t* offsets, uint32_t* ticket,
-                                unsigned long long* status, float* compact, uint32_t* err, int ordered, uint32_t* bad);
+                                unsigned long long* status, float* compact, uint32_t* err, int ordered, uint32_t* bad,
+                                bool whole);
+hipError_t launch_corner_box(hipStream_t, const RegionDesc*, const FTile* ftiles, uint32_t nft, const float* compact,
+                             float* out, const uint32_t* bad);
 
 // wc_pack.hip: the packed payload format's transcoders (k_pack_widths + k_pack_body, k_unpack)
 hipError_t launch_pack_units(hipStream_t, const PackDesc*, const FTile* tiles, uint32_t ntiles, const uint8_t* payload,
@@ -246,6 +245,9 @@ struct wc_ctx {
     // of the level passes (coef_extent / 8 floats); the call's levels and work
     // lists go through the same pinned block and tol_in
     wc::DevBuf lv_side;
+    // wc_inverse_coarse / wc_inverse_region: the call's descriptors on the host
+    // (kept between calls: a batch's 104 B per unit are not allocated anew each time)
+    std::vector<wc::RegionDesc> cdesc;
     // packed payloads (wc_pack / wc_unpack): the batch's descriptors and tiles
     // (PackDesc[n] | FTile[ntiles]) stay on the device while the units and the
     // value bytes recur (pk_key, pk_vbytes); the _host forms' staging
@@ -320,6 +322,10 @@ uint64_t rows_magic(int32_t d);
 // wc_regionhost.cpp (reduce NULL = all 0)
 int validate_region(wc_ctx* c, const wc_unit* units, int n, const int32_t* levels, const int32_t* reduce,
                     const wc_region* regions, const wc_unit* out_units);
+// the host driver of wc_inverse_coarse_host (regions NULL) and wc_inverse_region_host
+int inverse_compact_host(wc_ctx* c, const uint8_t* payload, const uint64_t* offsets, const wc_unit* units, int n,
+                         const int32_t* levels, const int32_t* reduce, const wc_region* regions,
+                         const wc_unit* out_units, float* out);
 
 // Bracket one launch with events when profiling is on.
 struct StageTimer {

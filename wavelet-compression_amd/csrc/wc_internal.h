@@ -84,42 +84,27 @@ struct FTile {
     uint32_t index;  // tile index within the unit
 };
 
-// One unit of the reduced-resolution inverse (wc_coarse.hip k_decode_corner):
-// the payload's box, the corner (w, h, d) = (W, H, D) >> r the call needs of it
-// and where the corner goes.  Built per call (the reduce is not part of a plan).
-struct CornerDesc {
-    uint64_t dst_off;   // element offset of the compact corner in the coefficient scratch (the derived unit's coef_off)
-    uint64_t out_off;   // the unit's first output cell
-    uint64_t dmagic;    // div_rows magic of D: row = floor(position / D)
-    uint64_t hmagic;    // div_rows magic of H: I = floor(row / H)
-    int32_t W, H, D;    // the payload's box
-    int32_t want;       // the header's ncoeff field: W*H*D, or -L for L >= 2
-    uint32_t w, h, d;   // the corner
-    uint32_t end;       // ((w-1)*H + (h-1))*D + d: no flat position at or past it is in the corner
-    uint32_t dt_begin;  // the unit's first look-back granule
-    uint32_t direct;    // 1: r == L, the corner is the result: k_corner_box copies it out, no pass or inverse runs
-};
-static_assert(sizeof(CornerDesc) == 72, "descriptor of 8-B members first");
-
-// One unit of the sub-box decode (wc_region.hip k_decode_region): the payload's
-// box, the primed unit (w, h, d) = (W, H, D) >> r with L' = L - r levels, and
-// the region's origin and extent in cells of that resolution (wc_regionmap.h).
-// Built per call.  The units with L' = 0 also get a CornerDesc (w, h, d = the
-// extent) for k_corner_box.
+// One unit of the reduced-resolution and of the sub-box decode (wc_region.hip
+// k_decode_region): the payload's box, the primed unit (w, h, d) = (W, H, D) >> r
+// with L' = L - r levels, and the region's origin and extent in cells of that
+// resolution (wc_regionmap.h).  wc_inverse_coarse's region is the whole primed
+// box: o = 0, s = (w, h, d).  Built per call (neither the reduce nor the region
+// is part of a plan).
 struct RegionDesc {
     uint64_t dst_off;      // element offset of the compact unit in the coefficient scratch (the derived unit's coef_off)
     uint64_t out_off;      // the unit's first output cell
-    uint64_t dmagic;       // div_rows magic of D
-    uint64_t hmagic;       // div_rows magic of H
+    uint64_t dmagic;       // div_rows magic of D: row = floor(position / D)
+    uint64_t hmagic;       // div_rows magic of H: I = floor(row / H)
     int32_t W, H, D;       // the payload's box
     int32_t want;          // the header's ncoeff field: W*H*D, or -L for L >= 2
     uint32_t w, h, d;      // the primed box
     uint32_t L;            // L' = L - r
     uint32_t ox, oy, oz;   // the region's origin >> r
     uint32_t sx, sy, sz;   // the region's extent >> r: the compact unit
-    uint32_t end;          // region_end: no needed pair at or past this flat position; 0: the region has no cells
+    uint32_t end;          // no needed pair at or past this flat position: region_end, or of the whole primed box
+                           // ((w-1)*H + (h-1))*D + d; 0: the region has no cells
     uint32_t dt_begin;     // the unit's first look-back granule
-    uint32_t direct;       // 1: L' = 0, the compact unit is the result (k_corner_box)
+    uint32_t direct;       // 1: L' = 0, the compact unit is the result: k_corner_box copies it out, no pass or inverse runs
     uint32_t pad;
 };
 static_assert(sizeof(RegionDesc) == 104, "descriptor of 8-B members first");
@@ -160,12 +145,12 @@ static_assert(sizeof(PackDesc) == 32, "descriptor of 8-B members first");
 constexpr int kPackTile = 2048;                        // pairs per transcoder workgroup (wc_pack.hip has the arithmetic)
 constexpr uint64_t kPackMaxCells = uint64_t(1) << 21;  // the device transcoders' largest unit (WC_PACK_MAX_CELLS)
 
-// Per-unit skip words (bad[u]) that k_decode<true> and k_decode_corner leave for
+// Per-unit skip words (bad[u]) that k_decode<true> and k_decode_region leave for
 // the launches after them: the level passes and k_inverse{,_fast}<true> skip a
 // unit unless its word is kUnitRun.
 constexpr uint32_t kUnitRun = 0u;      // the level passes and the one-level inverse run
 constexpr uint32_t kUnitRefused = 1u;  // the header disagrees: nothing more runs, the cells stay untouched
-constexpr uint32_t kUnitBox = 2u;      // wc_inverse_coarse, r == L: k_corner_box writes the cells, the rest skip
+constexpr uint32_t kUnitBox = 2u;      // wc_inverse_coarse and wc_inverse_region, r == L: k_corner_box writes the cells, the rest skip
 
 // Sentinel for a unit whose flat[0] is NaN: std::max_element then returns
 // flat[0] itself (every comparison with NaN is false), so thresh is NaN.

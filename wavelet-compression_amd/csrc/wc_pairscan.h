@@ -1,5 +1,5 @@
 // wc_pairscan.h — the pair-tile scan shared by the decoders: k_rowindex and
-// k_decode (wc_inverse.hip), k_decode_corner (wc_coarse.hip).
+// k_decode (wc_inverse.hip), k_decode_region (wc_region.hip).
 //
 // rle_decode (src/decompressor.cpp:14-30) puts pair k at flat position
 // p_k = (sum of run + 1 over pairs <= k) - 1.  A workgroup takes one pair tile
@@ -11,7 +11,7 @@
 // Which tiles run, and why no look-back waits on a tile that has left:
 //   - Each kernel derives from the header alone how many tiles T of the unit
 //     run (k_decode: the payload's pair tiles; k_rowindex: through the tile of
-//     the virtual pair k = nrle; k_decode_corner: min(pair tiles, ceil(end /
+//     the virtual pair k = nrle; k_decode_region: min(pair tiles, ceil(end /
 //     TILE)): a tile t >= T has its first pair index t*TILE >= end, so every
 //     pair of it and of every later tile lies at or past end).  Blocks whose
 //     plan index is >= T exit after the header, before any atomic.  In the
@@ -52,7 +52,7 @@ __device__ __forceinline__ uint32_t wave_incl_sum32_sat(uint32_t v) {
 // field `want` (W*H*D, or -L for a multi-level unit) and nrle >= 0.  More pairs
 // than coefficients are accepted: rle_decode drops every pair whose index
 // reaches ncoeff (src/decompressor.cpp:20-27), as the decoders do.  W, H, D:
-// fields of a UnitDev or a CornerDesc, by reference: one still in memory is
+// fields of a UnitDev or a RegionDesc, by reference: one still in memory is
 // loaded where it is compared.
 __device__ __forceinline__ bool header_ok(const int32_t& W, const int32_t& H, const int32_t& D, int32_t want,
                                           const uint8_t* __restrict__ ph, int32_t& nrle) {
@@ -67,7 +67,7 @@ __device__ __forceinline__ bool header_ok(const int32_t& W, const int32_t& H, co
 //   Sat32    32-bit saturating sums, a negative run counts as run 0, so
 //            positions never decrease.  Every position its users act on is
 //            below ncoeff < 2^31, and a sum clamped at 2^32 - 1 is past it like
-//            the exact one (k_rowindex, k_decode_corner).
+//            the exact one (k_rowindex, k_decode_region).
 //   Exact64  64-bit wrapping sums, a negative run adds (int64_t)run + 1:
 //            positions may step back (k_decode).
 struct Sat32 {

@@ -1,10 +1,11 @@
 // wc_regionhost.cpp — host side of the sub-box inverse (include/wavelet_amd.h
-// wc_inverse_region): the mode's argument checks and wc_inverse_region_host.
-// (wc_region_align and wc_region_units are in wc_regionrule.cpp, plain C++.)
+// wc_inverse_region): the mode's argument checks, wc_inverse_region_host and
+// the driver it shares with wc_inverse_coarse_host.  (wc_region_align and
+// wc_region_units are in wc_regionrule.cpp, plain C++.)
 //
-// The host entry point runs its unit runs (WC_OPT_HOST_CHUNK, by the cells of
-// the full-size units) one after another on the context's stream, as
-// wc_inverse_coarse_host does; only the regions' cells cross back.
+// The driver runs its unit runs (WC_OPT_HOST_CHUNK, by the cells of the
+// full-size units) one after another on the context's stream, as
+// wc_inverse_levels_host does; only the derived units' cells cross back.
 #include "wc_ctx.h"
 
 #include <algorithm>
@@ -62,19 +63,14 @@ int validate_region(wc_ctx* c, const wc_unit* units, int n, const int32_t* level
     return WC_OK;
 }
 
-}  // namespace wc
-
-extern "C" {
-
-int wc_inverse_region_host(wc_ctx* c, const uint8_t* payload, const uint64_t* offsets, const wc_unit* units, int n,
-                           const int32_t* levels, const int32_t* reduce, const wc_region* regions,
-                           const wc_unit* out_units, float* out) {
-    if (!c) return WC_ERR_INVALID;
+// wc_inverse_coarse_host (regions NULL) and wc_inverse_region_host after their
+// null checks: the levels (from the headers where the caller passes none), the
+// mode's checks, then run by run the upload, the device call and the readback.
+int inverse_compact_host(wc_ctx* c, const uint8_t* payload, const uint64_t* offsets, const wc_unit* units, int n,
+                         const int32_t* levels, const int32_t* reduce, const wc_region* regions,
+                         const wc_unit* out_units, float* out) {
     int rc;
-    if ((rc = validate_units(c, units, n))) return rc;
-    if (n == 0) return WC_OK;
-    if (!payload || !offsets || !regions || !out_units || !out) return fail(c, WC_ERR_INVALID, "null buffer");
-    // unit u's bytes: its header and the nrle pairs the header announces, as wc_inverse_coarse_host
+    // unit u's bytes: its header and the nrle pairs the header announces, as wc_inverse_levels_host
     std::vector<uint64_t> end(n);
     std::vector<int32_t> from_headers;
     if (!levels) from_headers.resize(n);
@@ -92,8 +88,11 @@ int wc_inverse_region_host(wc_ctx* c, const uint8_t* payload, const uint64_t* of
     }
     if (!levels) levels = from_headers.data();
     if ((rc = validate_levels(c, units, n, levels)) ||
-        (rc = validate_region(c, units, n, levels, reduce, regions, out_units)))
+        (rc = regions ? validate_region(c, units, n, levels, reduce, regions, out_units)
+                      : validate_coarse(c, units, n, levels, reduce, out_units)))
         return rc;
+    if (!regions && std::all_of(reduce, reduce + n, [](int32_t r) { return r == 0; }))
+        return wc_inverse_levels_host(c, payload, offsets, out_units, n, levels, out);
     if ((rc = set_device(c))) return rc;
     const uint64_t ext = cells_extent(out_units, n);
     const std::vector<int> rb = level_runs(c, units, n);
@@ -132,13 +131,18 @@ int wc_inverse_region_host(wc_ctx* c, const uint8_t* payload, const uint64_t* of
             (e = hipMemcpyAsync(c->h_offsets.p, ro.data(), sizeof(uint64_t) * m, hipMemcpyHostToDevice, c->stream)) !=
                 hipSuccess)
             return hip_fail(c, e, "payload upload");
-        if ((rc = wc_inverse_region(c, (const uint8_t*)c->h_payload.p, (const uint64_t*)c->h_offsets.p, units + a, m,
-                                    levels + a, reduce ? reduce + a : nullptr, regions + a, out_units + a,
-                                    (float*)c->h_out.p))) {
+        const uint8_t* d_payload = (const uint8_t*)c->h_payload.p;
+        const uint64_t* d_offsets = (const uint64_t*)c->h_offsets.p;
+        float* d_out = (float*)c->h_out.p;
+        rc = regions ? wc_inverse_region(c, d_payload, d_offsets, units + a, m, levels + a,
+                                         reduce ? reduce + a : nullptr, regions + a, out_units + a, d_out)
+                     : wc_inverse_coarse(c, d_payload, d_offsets, units + a, m, levels + a, reduce + a, out_units + a,
+                                         d_out);
+        if (rc) {
             (void)hipStreamSynchronize(c->stream);
             return rc;
         }
-        // the regions' boxes, back-to-back ones in one copy (cells no unit owns stay as they were)
+        // the units' boxes, back-to-back ones in one copy (cells no unit owns stay as they were)
         e = hipSuccess;
         for (int i = a; i < a + m && e == hipSuccess;) {
             uint64_t lo = out_units[i].cell_offset,
@@ -146,7 +150,7 @@ int wc_inverse_region_host(wc_ctx* c, const uint8_t* payload, const uint64_t* of
             for (++i; i < a + m && out_units[i].cell_offset == hi; ++i)
                 hi += (uint64_t)out_units[i].nx * out_units[i].ny * out_units[i].nz;
             if (hi > lo)
-                e = hipMemcpyAsync(out + lo, (const float*)c->h_out.p + lo, sizeof(float) * (hi - lo),
+                e = hipMemcpyAsync(out + lo, (const float*)d_out + lo, sizeof(float) * (hi - lo),
                                    hipMemcpyDeviceToHost, c->stream);
         }
         // ro is rewritten by the next run: the uploads have finished after this synchronize
@@ -154,6 +158,21 @@ int wc_inverse_region_host(wc_ctx* c, const uint8_t* payload, const uint64_t* of
         if (e != hipSuccess || es != hipSuccess) return hip_fail(c, e != hipSuccess ? e : es, "box readback");
     }
     return check_kernel_errors(c);
+}
+
+}  // namespace wc
+
+extern "C" {
+
+int wc_inverse_region_host(wc_ctx* c, const uint8_t* payload, const uint64_t* offsets, const wc_unit* units, int n,
+                           const int32_t* levels, const int32_t* reduce, const wc_region* regions,
+                           const wc_unit* out_units, float* out) {
+    if (!c) return WC_ERR_INVALID;
+    int rc;
+    if ((rc = validate_units(c, units, n))) return rc;
+    if (n == 0) return WC_OK;
+    if (!payload || !offsets || !regions || !out_units || !out) return fail(c, WC_ERR_INVALID, "null buffer");
+    return inverse_compact_host(c, payload, offsets, units, n, levels, reduce, regions, out_units, out);
 }
 
 }  // extern "C"
