@@ -71,9 +71,13 @@ __global__ __launch_bounds__(kThreads, WC_RIX_MINB) void k_rowindex(const UnitDe
     const bool hok = header_ok(U.nx, U.ny, U.nz, (int32_t)U.ncells, ph, nrle);
     const uint32_t n = hok ? (uint32_t)nrle : 0u;
     if (ft.index == 0 && tid == 0) npairs[u] = n;  // K6r bounds its pair indices by it
-    // tiles up to the one holding the virtual pair k = n (the plan launches
-    // floor(ncoeff / kRixTile) + 1, enough for the first dropped pair)
-    const uint32_t ntile = n / (uint32_t)kRixTile + 1u;
+    // tiles up to the one holding the virtual pair k = n, and no more than the
+    // plan launched (U.ndt = floor(ncoeff / kRixTile) + 1, enough for the first
+    // dropped pair, k = ncoeff, which closes the table like the virtual one).
+    // Without the bound a payload with a tile or more of surplus pairs gives
+    // the reversed order tiles past the unit's granules and never runs the
+    // first ones.
+    const uint32_t ntile = min(n / (uint32_t)kRixTile + 1u, U.ndt);
     if (ft.index >= ntile) return;  // uniform; before any atomic (wc_pairscan.h)
     using Scan = PairScan<Sat32, GranuleEpoch32, kRixTile, LoadRuns>;
     const uint32_t t = Scan::tile_index(ft.index, ntile, ordered, ticket + u, s_x);
@@ -151,10 +155,13 @@ __global__ __launch_bounds__(kThreads) void k_decode(const UnitDev* __restrict__
         if (!hok) return;  // uniform
     }
     const int64_t n = hok ? nrle : 0;
-    const uint32_t ntile = n ? (uint32_t)((n + kFlatTile - 1) / kFlatTile) : 1u;
-    // The plan launches ceil(ncoeff / kFlatTile) blocks per unit; those whose
-    // plan index is past the payload's pair tiles exit before any atomic
-    // (wc_pairscan.h).
+    // The plan launches U.ndt = ceil(ncoeff / kFlatTile) blocks per unit; those
+    // whose plan index is past the payload's pair tiles exit before any atomic
+    // (wc_pairscan.h).  A payload with more pair tiles than that (surplus
+    // pairs, all at or past ncoeff: every pair adds at least 1) runs the first
+    // U.ndt: the last of them writes through ncoeff - 1, and the reversed
+    // order stays inside the tiles that were launched and their granules.
+    const uint32_t ntile = n ? (uint32_t)min((n + kFlatTile - 1) / kFlatTile, (int64_t)U.ndt) : 1u;
     if (ft.index >= ntile) return;  // uniform
     const uint32_t t = Scan::tile_index(ft.index, ntile, ordered, ticket + u, s_x);
     if (!hok && t == 0 && tid == 0) atomicOr(err, kErrHeader);

@@ -11,7 +11,10 @@
 // Which tiles run, and why no look-back waits on a tile that has left:
 //   - Each kernel derives from the header alone how many tiles T of the unit
 //     run (k_decode: the payload's pair tiles; k_rowindex: through the tile of
-//     the virtual pair k = nrle; k_decode_region: min(pair tiles, ceil(end /
+//     the virtual pair k = nrle; both: at most the tiles the plan launched for
+//     the unit, which hold every pair below ncoeff whatever the surplus, so
+//     that T - 1 - index never names a tile without a block or a granule;
+//     k_decode_region: min(pair tiles, ceil(end /
 //     TILE)): a tile t >= T has its first pair index t*TILE >= end, so every
 //     pair of it and of every later tile lies at or past end).  Blocks whose
 //     plan index is >= T exit after the header, before any atomic.  In the
@@ -93,8 +96,11 @@ struct Exact64 {
         return v;
     }
     static __device__ __forceinline__ T last(T s) {
-        return ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(s >> 32), 63) << 32) |
-               __builtin_amdgcn_readlane((uint32_t)s, 63);
+        // through uint32_t: the builtin returns int, and a low half with bit 31
+        // set (a sum past 2^31 - 1) would sign-extend over the high half
+        const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)s, 63);
+        const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(s >> 32), 63);
+        return ((uint64_t)hi << 32) | lo;
     }
 };
 
