@@ -679,10 +679,11 @@ int wc_inverse_region_host(wc_ctx* ctx, const uint8_t* payload, const uint64_t* 
  * payload's kept coefficients.  A standard payload spends 8 bytes per pair, an
  * int32 run and an fp32 value; a packed unit stores each chunk of 64 pairs as
  * bit planes of the runs at the chunk's own width and as the top 2, 3 or 4 bytes
- * of the values in byte planes.  No decoder reads the packed format: wc_unpack
- * restores standard payloads and every decoder reads those unchanged.  Every
- * existing entry point rejects a packed unit (WC_ERR_FORMAT), its ncoeff field
- * being neither W*H*D nor -2..-4.
+ * of the values in byte planes.  wc_unpack restores standard payloads, which
+ * every decoder reads unchanged; wc_inverse_packed, wc_inverse_packed_coarse and
+ * wc_inverse_packed_region (below) decode packed units directly.  Every other
+ * entry point rejects a packed unit (WC_ERR_FORMAT), its ncoeff field being
+ * neither W*H*D nor -2..-4.
  *
  * Format of one unit (integers little-endian).  V = value bytes, 2..4; L = the
  * source payload's levels, 1..WC_MAX_LEVELS; n = its nrle; nch = ceil(n / 64);
@@ -783,6 +784,60 @@ int wc_pack_host(wc_ctx* ctx, const uint8_t* payload, const uint64_t* offsets, c
                  uint8_t* packed, uint64_t packed_capacity, uint64_t* packed_offsets, uint64_t* packed_bytes);
 int wc_unpack_host(wc_ctx* ctx, const uint8_t* packed, const uint64_t* packed_offsets, const wc_unit* units, int n,
                    uint8_t* payload, uint64_t payload_capacity, uint64_t* offsets, uint32_t* kept);
+
+/* Decoding packed units directly: the dense decode (wc_inverse_levels), the
+ * reduced-resolution decode (wc_inverse_coarse) and the sub-box decode
+ * (wc_inverse_region) with packed units as their source.  Each call gives, bit
+ * for bit (NaN payload bits included), what wc_unpack followed by its standard
+ * twin gives on the same units: the same kernels run the same scan, scatter and
+ * synthesis, and only the load of a tile's pairs differs (a decode tile is 64
+ * chunks; a workgroup places its chunks from the width table as wc_unpack does).
+ * No standard payload is written and nothing is sized by wc_payload_bound; the
+ * coarse and the sub-box decode keep their "only the pair tiles before `end`"
+ * property, and read of those tiles only the table, the planes and the values.
+ *   wc_inverse_packed: EVERY unit of the call is a packed unit at d_packed +
+ *     d_packed_offsets[u] (each == 4 mod 8; the slots of wc_pack or the dense
+ *     layout of wc_pack_host; d_packed 8-byte aligned); a mixed batch is the
+ *     caller's to split.  levels (HOST, consumed before return; NULL = all 1) as
+ *     in wc_inverse_levels.  Every unit decodes densely, for every L, L = 1 units
+ *     of any dimensions included (the row-indexed inverse reads pairs at random
+ *     from a standard payload and has no packed form).  Books WC_STAGE_DECODE,
+ *     WC_STAGE_LEVELS and WC_STAGE_INVERSE like wc_inverse_levels.
+ *   wc_inverse_packed_coarse / wc_inverse_packed_region: levels, reduce, regions
+ *     and out_units exactly as in wc_inverse_coarse / wc_inverse_region.
+ *   Nothing at or past packed_capacity is read.  Refusals on the device
+ *   (WC_ERR_FORMAT at the next wc_synchronize; the other units decode): an offset
+ *   that is not 4 (mod 8), a header that is not a packed one of its unit with the
+ *   expected L, n above the cell count, a table whose end would pass the capacity:
+ *   the unit's output cells stay untouched, as in the standard decoders; a width
+ *   above 31 or a chunk whose end would pass the capacity: the unit's cells are
+ *   unspecified, and nothing is written outside the unit's own scratch and output
+ *   range.  A packed run has at most 31 bits, so no negative run can arise.  A
+ *   unit whose region has no cells reads nothing, its header included.  Before
+ *   anything is launched (WC_ERR_INVALID, outputs untouched): what the standard
+ *   twin refuses, null buffers, a unit above WC_PACK_MAX_CELLS cells.
+ *   _host forms: host buffers; levels = NULL reads each L from its unit's tag;
+ *     the packed bytes are uploaded (not standard payloads), the unit runs
+ *     (WC_OPT_HOST_CHUNK) go one after another, only the result cells cross back.
+ *     Every unit is checked on the host first (wc_packed_size): a unit the device
+ *     would refuse fails the call (WC_ERR_FORMAT) and leaves the outputs untouched.
+ * Measured at C2 (profiles/r17/packed_decode.json, DESIGN.md "Packed decode"). */
+int wc_inverse_packed(wc_ctx* ctx, const uint8_t* d_packed, const uint64_t* d_packed_offsets, uint64_t packed_capacity,
+                      const wc_unit* units, int n, const int32_t* levels, float* d_out);
+int wc_inverse_packed_coarse(wc_ctx* ctx, const uint8_t* d_packed, const uint64_t* d_packed_offsets,
+                             uint64_t packed_capacity, const wc_unit* units, int n, const int32_t* levels,
+                             const int32_t* reduce, const wc_unit* out_units, float* d_out);
+int wc_inverse_packed_region(wc_ctx* ctx, const uint8_t* d_packed, const uint64_t* d_packed_offsets,
+                             uint64_t packed_capacity, const wc_unit* units, int n, const int32_t* levels,
+                             const int32_t* reduce, const wc_region* regions, const wc_unit* out_units, float* d_out);
+int wc_inverse_packed_host(wc_ctx* ctx, const uint8_t* packed, const uint64_t* packed_offsets, const wc_unit* units,
+                           int n, const int32_t* levels, float* out);
+int wc_inverse_packed_coarse_host(wc_ctx* ctx, const uint8_t* packed, const uint64_t* packed_offsets,
+                                  const wc_unit* units, int n, const int32_t* levels, const int32_t* reduce,
+                                  const wc_unit* out_units, float* out);
+int wc_inverse_packed_region_host(wc_ctx* ctx, const uint8_t* packed, const uint64_t* packed_offsets,
+                                  const wc_unit* units, int n, const int32_t* levels, const int32_t* reduce,
+                                  const wc_region* regions, const wc_unit* out_units, float* out);
 
 /* Transform only: cells -> flat fp32 coefficients (x-slowest order), written
  * at the same element offsets as the cells (d_flat has the cell buffer's extent). */

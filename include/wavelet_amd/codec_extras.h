@@ -76,7 +76,10 @@ std::vector<CompressedWavelet> compress_budget(multiBox3D& box, std::vector<int>
 // value stored in its top `vbytes` bytes (4: lossless; 3, 2: rounded to nearest even,
 // an added error of at most 2^-16 or 2^-8 of the box's norm), the runs as bit planes.
 // Same file names; decompress(), decompress_coarse() and decompress_region() recognise
-// such files by their headers and unpack them first (wc_unpack_host).  The returned
+// such files by their headers: decompress() and decompress_coarse() decode them from their
+// packed bytes (wc_inverse_packed_host, wc_inverse_packed_coarse_host: the bits of unpacking
+// first, without the standard payload); decompress_region() unpacks them first
+// (wc_unpack_host), the path that measured faster for a region.  The returned
 // structs describe the payloads before packing.  vbytes outside 2..4 or a component
 // of more than WC_PACK_MAX_CELLS cells: it exits with a message, as the other errors do.
 std::vector<CompressedWavelet> compress_packed(multiBox3D& box, std::vector<int> components, double keep, int vbytes,

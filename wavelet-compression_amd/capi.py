@@ -39,6 +39,8 @@ EXPORTED = (
     "wc_budget_thresholds", "wc_budget_select", "wc_forward_levels_budget", "wc_forward_levels_budget_host",
     "wc_pack_value", "wc_packed_tag", "wc_payload_packed", "wc_packed_size", "wc_pack_unit", "wc_unpack_unit",
     "wc_packed_bound", "wc_pack", "wc_unpack", "wc_pack_host", "wc_unpack_host",
+    "wc_inverse_packed", "wc_inverse_packed_coarse", "wc_inverse_packed_region",
+    "wc_inverse_packed_host", "wc_inverse_packed_coarse_host", "wc_inverse_packed_region_host",
 )
 WC_MAX_LEVELS = 4  # levels of the opt-in multi-level transform (1 = the reference's codec)
 WC_PACK_MAX_CELLS = 1 << 21  # the largest unit wc_pack / wc_unpack take (the host rule has no limit)
@@ -176,6 +178,12 @@ def load_library() -> ctypes.CDLL:
         "wc_unpack": (i32, [vp, vp, vp, u64, up, i32, vp, u64, vp, vp]),
         "wc_pack_host": (i32, [vp, vp, vp, up, i32, i32, vp, u64, vp, vp]),
         "wc_unpack_host": (i32, [vp, vp, vp, up, i32, vp, u64, vp, vp]),
+        "wc_inverse_packed": (i32, [vp, vp, vp, u64, up, i32, vp, vp]),
+        "wc_inverse_packed_coarse": (i32, [vp, vp, vp, u64, up, i32, vp, vp, up, vp]),
+        "wc_inverse_packed_region": (i32, [vp, vp, vp, u64, up, i32, vp, vp, rp, up, vp]),
+        "wc_inverse_packed_host": (i32, [vp, vp, vp, up, i32, vp, vp]),
+        "wc_inverse_packed_coarse_host": (i32, [vp, vp, vp, up, i32, vp, vp, up, vp]),
+        "wc_inverse_packed_region_host": (i32, [vp, vp, vp, up, i32, vp, vp, rp, up, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -446,6 +454,36 @@ class Context:
                                       int(packed_capacity), units, n, ctypes.c_void_p(d_payload), int(capacity),
                                       ctypes.c_void_p(d_offsets), ctypes.c_void_p(d_kept)))
 
+    def inverse_packed(self, d_packed: int, d_packed_offsets: int, packed_capacity: int, units, n: int, levels,
+                       d_out: int):
+        """wc_inverse_packed: packed units -> boxes, bit for bit unpack +
+        inverse_levels without the standard payloads.  levels None: all 1."""
+        lv = None if levels is None else _levels_array(levels, n)
+        self._check(self._L.wc_inverse_packed(self._h, ctypes.c_void_p(d_packed), ctypes.c_void_p(d_packed_offsets),
+                                              int(packed_capacity), units, n, None if lv is None else lv.ctypes.data,
+                                              ctypes.c_void_p(d_out)))
+
+    def inverse_packed_coarse(self, d_packed: int, d_packed_offsets: int, packed_capacity: int, units, n: int, levels,
+                              reduce, out_units, d_out: int):
+        """wc_inverse_packed_coarse: inverse_coarse with packed units as its source."""
+        lv = None if levels is None else _levels_array(levels, n)
+        rd = _levels_array(reduce, n)
+        self._check(self._L.wc_inverse_packed_coarse(self._h, ctypes.c_void_p(d_packed),
+                                                     ctypes.c_void_p(d_packed_offsets), int(packed_capacity), units, n,
+                                                     None if lv is None else lv.ctypes.data, rd.ctypes.data, out_units,
+                                                     ctypes.c_void_p(d_out)))
+
+    def inverse_packed_region(self, d_packed: int, d_packed_offsets: int, packed_capacity: int, units, n: int, levels,
+                              reduce, regions, out_units, d_out: int):
+        """wc_inverse_packed_region: inverse_region with packed units as its source."""
+        lv = None if levels is None else _levels_array(levels, n)
+        rd = None if reduce is None else _levels_array(reduce, n)
+        self._check(self._L.wc_inverse_packed_region(self._h, ctypes.c_void_p(d_packed),
+                                                     ctypes.c_void_p(d_packed_offsets), int(packed_capacity), units, n,
+                                                     None if lv is None else lv.ctypes.data,
+                                                     None if rd is None else rd.ctypes.data, make_regions(regions, n),
+                                                     out_units, ctypes.c_void_p(d_out)))
+
     def decompose(self, d_cells: int, dtype: int, units, n: int, d_flat: int):
         self._check(self._L.wc_decompose(self._h, ctypes.c_void_p(d_cells), dtype, units, n,
                                          ctypes.c_void_p(d_flat)))
@@ -676,6 +714,46 @@ class Context:
         self._check(self._L.wc_unpack_host(self._h, p.ctypes.data, o.ctypes.data, units, n, payload.ctypes.data, cap,
                                            offsets.ctypes.data, kept.ctypes.data))
         return payload, offsets, kept[:n]
+
+    def _packed_host_args(self, packed, packed_offsets, n, extent, levels, out):
+        p = np.ascontiguousarray(packed, dtype=np.uint8)
+        o = np.ascontiguousarray(packed_offsets, dtype=np.uint64)
+        lv = None if levels is None else _levels_array(levels, n)
+        if out is None:
+            out = np.zeros(max(extent, 1), np.float32)
+        elif out.dtype != np.float32 or out.size < extent or not out.flags.c_contiguous:
+            raise ValueError("out: contiguous float32[>= extent]")
+        return p, o, lv, out
+
+    def inverse_packed_host(self, packed: np.ndarray, packed_offsets: np.ndarray, units, n: int, extent: int,
+                            levels=None, out=None):
+        """wc_inverse_packed_host: packed units (host, each offset == 4 mod 8) ->
+        float32[extent] boxes; levels None: each unit's L is read from its tag."""
+        p, o, lv, out = self._packed_host_args(packed, packed_offsets, n, extent, levels, out)
+        self._check(self._L.wc_inverse_packed_host(self._h, p.ctypes.data, o.ctypes.data, units, n,
+                                                   None if lv is None else lv.ctypes.data, out.ctypes.data))
+        return out[:extent]
+
+    def inverse_packed_coarse_host(self, packed: np.ndarray, packed_offsets: np.ndarray, units, n: int, reduce,
+                                   out_units, extent: int, levels=None, out=None):
+        """wc_inverse_packed_coarse_host -> float32[extent] coarse boxes at out_units' offsets."""
+        p, o, lv, out = self._packed_host_args(packed, packed_offsets, n, extent, levels, out)
+        rd = _levels_array(reduce, n)
+        self._check(self._L.wc_inverse_packed_coarse_host(self._h, p.ctypes.data, o.ctypes.data, units, n,
+                                                          None if lv is None else lv.ctypes.data, rd.ctypes.data,
+                                                          out_units, out.ctypes.data))
+        return out[:extent]
+
+    def inverse_packed_region_host(self, packed: np.ndarray, packed_offsets: np.ndarray, units, n: int, reduce,
+                                   regions, out_units, extent: int, levels=None, out=None):
+        """wc_inverse_packed_region_host -> float32[extent] region boxes at out_units' offsets; reduce None: all 0."""
+        p, o, lv, out = self._packed_host_args(packed, packed_offsets, n, extent, levels, out)
+        rd = None if reduce is None else _levels_array(reduce, n)
+        self._check(self._L.wc_inverse_packed_region_host(self._h, p.ctypes.data, o.ctypes.data, units, n,
+                                                          None if lv is None else lv.ctypes.data,
+                                                          None if rd is None else rd.ctypes.data,
+                                                          make_regions(regions, n), out_units, out.ctypes.data))
+        return out[:extent]
 
     def forward_host_units(self, boxes, units, n: int, keep: float):
         """wc_forward_host_units: unit u's cells from boxes[u] (its own host

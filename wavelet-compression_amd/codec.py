@@ -166,8 +166,7 @@ def unpack_payloads(packed: Sequence[bytes], device: int = 0) -> List[bytes]:
 
 def _standard_payloads(payloads: Sequence[bytes], device: int = 0) -> List[bytes]:
     """The list with its packed units (capi.payload_packed) unpacked; a list without any is returned as it is."""
-    which = [i for i, p in enumerate(payloads) if len(p) >= 20 and int(np.frombuffer(p[12:16], "<i4")[0]) < -capi.WC_MAX_LEVELS
-             and capi.payload_packed(p)[1]]
+    which = _packed_indices(payloads)
     if not which:
         return list(payloads)
     out = list(payloads)
@@ -348,25 +347,60 @@ def decompress_payloads(payloads: Sequence[bytes], device: int = 0, coarsen: int
     depends on alone (wc_inverse_region_host) and cropped here.  The bits are
     those of the crop of the full decode.
 
-    Packed units (compress_payloads(pack=)) are recognised by their headers and
-    unpacked first (wc_unpack_host), alone or mixed with standard payloads, on
-    every path above."""
-    payloads = _standard_payloads(payloads, device)
+    Packed units (compress_payloads(pack=)) are recognised by their headers.  The
+    full and the coarsen= decode read them directly from their packed bytes
+    (wc_inverse_packed_host, wc_inverse_packed_coarse_host): no standard payload
+    is rebuilt, and the bits are those of unpack_payloads followed by the
+    standard call.  A list that mixes packed and standard payloads makes two
+    calls, one per kind, and the boxes come back in list order.  With region=
+    the packed units are unpacked first (wc_unpack_host): the direct region call
+    measured slower than unpack + decode on the device (DESIGN.md "Packed
+    decode"); capi's inverse_packed_region_host is there for a caller who wants
+    the smaller footprint."""
+    if region is not None:
+        payloads = _standard_payloads(payloads, device)
+    payloads = list(payloads)
+    which = _packed_indices(payloads)
+    if which and len(which) < len(payloads):
+        rest = [i for i in range(len(payloads)) if i not in set(which)]
+        out = [None] * len(payloads)
+        for idx, packed in ((which, True), (rest, False)):
+            for i, box in zip(idx, _decompress_group([payloads[i] for i in idx], device, coarsen, region, packed)):
+                out[i] = box
+        return out
+    return _decompress_group(payloads, device, coarsen, region, bool(which))
+
+
+def _packed_indices(payloads: Sequence[bytes]) -> list:
+    """The indices of the list's packed units (capi.payload_packed)."""
+    return [i for i, p in enumerate(payloads) if len(p) >= 20 and int(np.frombuffer(p[12:16], "<i4")[0]) < -capi.WC_MAX_LEVELS
+            and capi.payload_packed(p)[1]]
+
+
+def _decompress_group(payloads: Sequence[bytes], device: int, coarsen: int, region, packed: bool) -> List[np.ndarray]:
+    """decompress_payloads on payloads of one kind: standard ones, or packed units (packed)."""
     dims = []
     multi = False
+    heads = []  # what the checks below read of a payload: its header with the standard ncoeff field
     for p in payloads:
-        h = np.frombuffer(p[:20], "<i4")
+        h = np.frombuffer(p[:20], "<i4").copy()
         dims.append((int(h[0]), int(h[1]), int(h[2])))
+        if packed:
+            L = capi.payload_packed(p)[0]
+            h[3] = -L if L >= 2 else int(h[0]) * int(h[1]) * int(h[2])
+        heads.append(h.tobytes())
         multi |= int(h[3]) < 0
-    cdims = _coarse_dims(payloads, dims, coarsen)
+    cdims = _coarse_dims(heads, dims, coarsen)
     if region is not None:
-        lo, hi, regions = _aligned_regions(payloads, dims, region)
+        lo, hi, regions = _aligned_regions(heads, dims, region)
     units, n, extent = capi.make_units(dims)
     buf, offsets = _laid_out(payloads)
+    ctx = context(device)
     if region is not None:
         r = int(coarsen)
         out_units, extent = capi.region_units(units, n, regions, r)
-        flat = context(device).inverse_region_host(buf, offsets, units, n, r, regions, out_units, extent)
+        assert not packed  # decompress_payloads unpacks first for a region
+        flat = ctx.inverse_region_host(buf, offsets, units, n, r, regions, out_units, extent)
         up = (1 << r) - 1
         out = []
         for i, g in enumerate(regions):
@@ -379,12 +413,15 @@ def decompress_payloads(payloads: Sequence[bytes], device: int = 0, coarsen: int
         return out
     if coarsen:
         out_units, extent = capi.coarse_units(units, n, int(coarsen))
-        flat = context(device).inverse_coarse_host(buf, offsets, units, n, int(coarsen), out_units, extent)
+        call = ctx.inverse_packed_coarse_host if packed else ctx.inverse_coarse_host
+        flat = call(buf, offsets, units, n, int(coarsen), out_units, extent)
         units, dims = out_units, cdims
+    elif packed:
+        flat = ctx.inverse_packed_host(buf, offsets, units, n, extent)
     elif multi:
-        flat = context(device).inverse_levels_host(buf, offsets, units, n, extent)
+        flat = ctx.inverse_levels_host(buf, offsets, units, n, extent)
     else:
-        flat = context(device).inverse_host(buf, offsets, units, n, extent)
+        flat = ctx.inverse_host(buf, offsets, units, n, extent)
     out = []
     for i, (W, H, D) in enumerate(dims):
         o = units[i].cell_offset

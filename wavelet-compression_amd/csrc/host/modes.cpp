@@ -319,73 +319,60 @@ std::string unit_name(int t, int lev, int comp, int box) {
            std::to_string(box) + ".xz";
 }
 
-// Payloads -> one buffer for wc_inverse_host (offsets = 4 mod 8: pairs 8-B aligned).
-// Files written with pack= are recognised by their headers and unpacked first, all of a batch in one call.
-void unpack_batch(std::vector<std::string>& payloads, const std::vector<wc_unit>& units) {
-    std::vector<size_t> which;
-    std::vector<wc_unit> pu;
-    std::vector<uint64_t> offs;
-    uint64_t cur = 4;
-    for (size_t i = 0; i < payloads.size(); ++i) {
-        const std::string& p = payloads[i];
-        int L = 0, V = 0;
-        if (p.size() < 20 || wc_payload_packed(reinterpret_cast<const uint8_t*>(p.data()), 20, &L, &V) != WC_OK || V == 0)
-            continue;  // a standard payload, or a header the decoder refuses in its own words
-        uint64_t len = 0;
-        if (wc_packed_size(reinterpret_cast<const uint8_t*>(p.data()), p.size(), &len) != WC_OK || len > p.size())
-            fatal("Deserialization failed: truncated or malformed packed payload");
-        which.push_back(i);
-        pu.push_back(units[i]);
-        offs.push_back(cur);
-        cur += (p.size() + 7) / 8 * 8;
-    }
-    if (which.empty()) return;
-    std::vector<uint8_t> buf(cur + 8, 0);
-    for (size_t k = 0; k < which.size(); ++k)
-        std::memcpy(buf.data() + offs[k], payloads[which[k]].data(), payloads[which[k]].size());
-    const int n = (int)which.size();
-    const uint64_t cap = wc_payload_bound(pu.data(), n);
-    std::unique_ptr<uint8_t[]> out(new uint8_t[cap]);
-    std::vector<uint64_t> oo(n + 1);
-    std::vector<uint32_t> kept(n);
-    wc_ctx* ctx = thread_ctx();
-    check(ctx, wc_unpack_host(ctx, buf.data(), offs.data(), pu.data(), n, out.get(), cap, oo.data(), kept.data()),
-          "GPU unpack");
-    for (int k = 0; k < n; ++k)
-        payloads[which[k]].assign(reinterpret_cast<const char*>(out.get() + oo[k]), 20 + 8ull * kept[k]);
+// Payloads -> one buffer for the _host decoders (offsets = 4 mod 8: pairs and packed chunks 8-B aligned).
+// Files written with pack= are recognised by their headers and decoded from their packed bytes
+// (wc_inverse_packed_host), all of a batch in one call; a batch that also holds standard payloads makes a
+// second call for those.  Each call writes only its own units' cells of `out`.
+bool is_packed(const std::string& p) {
+    int L = 0, V = 0;
+    if (p.size() < 20 || wc_payload_packed(reinterpret_cast<const uint8_t*>(p.data()), 20, &L, &V) != WC_OK || V == 0)
+        return false;  // a standard payload, or a header the decoder refuses in its own words
+    uint64_t len = 0;
+    if (wc_packed_size(reinterpret_cast<const uint8_t*>(p.data()), p.size(), &len) != WC_OK || len > p.size())
+        fatal("Deserialization failed: truncated or malformed packed payload");
+    return true;
 }
 
 void inverse_batch(std::vector<std::string>& payloads, const std::vector<wc_unit>& units, float* out) {
-    unpack_batch(payloads, units);
-    std::vector<uint64_t> offs(payloads.size());
-    uint64_t cur = 4;
-    for (size_t i = 0; i < payloads.size(); ++i) {
-        if (payloads[i].size() < 20) fatal("Deserialization failed: payload shorter than its header");
-        // wc_inverse_host sizes the device copy from each header's nrle: a truncated
-        // or corrupt stream must not make it read past this buffer
-        int32_t nrle;
-        std::memcpy(&nrle, payloads[i].data() + 16, 4);
-        if (nrle < 0 || 20 + 8 * (uint64_t)nrle > payloads[i].size())
-            fatal("Deserialization failed: payload holds fewer pairs than its header's nrle");
-        offs[i] = cur;
-        cur += (payloads[i].size() + 4 + 7) / 8 * 8;
-    }
-    std::vector<uint8_t> buf(cur + 8, 0);
-    for (size_t i = 0; i < payloads.size(); ++i) std::memcpy(buf.data() + offs[i], payloads[i].data(), payloads[i].size());
     wc_ctx* ctx = thread_ctx();
-    // a multi-level file (levels= at -c) carries ncoeff = -L: such a batch takes the levels from the headers
-    bool multi = false;
-    for (const std::string& p : payloads) {
-        int32_t ncoeff;
-        std::memcpy(&ncoeff, p.data() + 12, 4);
-        multi |= ncoeff < 0;
+    for (int packed = 1; packed >= 0; --packed) {
+        std::vector<const std::string*> ps;
+        std::vector<wc_unit> us;
+        for (size_t i = 0; i < payloads.size(); ++i)
+            if (is_packed(payloads[i]) == (packed != 0)) {
+                ps.push_back(&payloads[i]);
+                us.push_back(units[i]);
+            }
+        if (ps.empty()) continue;
+        std::vector<uint64_t> offs(ps.size());
+        uint64_t cur = 4;
+        bool multi = false;  // a multi-level file (levels= at -c) carries ncoeff = -L: such a batch takes the levels from the headers
+        for (size_t i = 0; i < ps.size(); ++i) {
+            const std::string& p = *ps[i];
+            if (p.size() < 20) fatal("Deserialization failed: payload shorter than its header");
+            if (!packed) {
+                // wc_inverse_host sizes the device copy from each header's nrle: a truncated
+                // or corrupt stream must not make it read past this buffer
+                int32_t ncoeff, nrle;
+                std::memcpy(&ncoeff, p.data() + 12, 4);
+                std::memcpy(&nrle, p.data() + 16, 4);
+                if (nrle < 0 || 20 + 8 * (uint64_t)nrle > p.size())
+                    fatal("Deserialization failed: payload holds fewer pairs than its header's nrle");
+                multi |= ncoeff < 0;
+            }
+            offs[i] = cur;
+            cur += (p.size() + 4 + 7) / 8 * 8;
+        }
+        std::vector<uint8_t> buf(cur + 8, 0);
+        for (size_t i = 0; i < ps.size(); ++i) std::memcpy(buf.data() + offs[i], ps[i]->data(), ps[i]->size());
+        const int n = (int)us.size();
+        if (packed)
+            check(ctx, wc_inverse_packed_host(ctx, buf.data(), offs.data(), us.data(), n, nullptr, out), "GPU decompress");
+        else if (multi)
+            check(ctx, wc_inverse_levels_host(ctx, buf.data(), offs.data(), us.data(), n, nullptr, out), "GPU decompress");
+        else
+            check(ctx, wc_inverse_host(ctx, buf.data(), offs.data(), us.data(), n, out), "GPU decompress");
     }
-    if (multi)
-        check(ctx, wc_inverse_levels_host(ctx, buf.data(), offs.data(), units.data(), (int)units.size(), nullptr, out),
-              "GPU decompress");
-    else
-        check(ctx, wc_inverse_host(ctx, buf.data(), offs.data(), units.data(), (int)units.size(), out),
-              "GPU decompress");
 }
 
 // The run's cells over all (t, lev, box) and selected components.

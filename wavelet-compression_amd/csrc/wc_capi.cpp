@@ -978,10 +978,13 @@ void compact_desc(RegionDesc& d, const wc_unit& f, const wc_unit& o, int L, int 
 // scratch and runs the remaining L - r levels and the one-level inverse on it,
 // as wc_inverse_levels does on full arrays.  Both are dense plans
 // (WC_OPT_INVERSE_ROWS = 0) and stay in the plan cache.
+// packed_cap: d_payload holds packed units, read below *packed_cap (wc_inverse_packed_coarse / _region).
 int inverse_compact(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
-                    const wc_unit* out_units, float* d_out, std::vector<RegionDesc>& desc, bool whole) {
+                    const wc_unit* out_units, float* d_out, std::vector<RegionDesc>& desc, bool whole,
+                    const uint64_t* packed_cap = nullptr) {
     int rc;
-    if ((rc = check_aligned(c, d_payload, "payload")) || (rc = check_aligned(c, d_offsets, "offsets", 8)) ||
+    if ((rc = check_aligned(c, d_payload, "payload", packed_cap ? 8 : 16)) ||  // packed: as wc_unpack
+        (rc = check_aligned(c, d_offsets, "offsets", 8)) ||
         (rc = check_aligned(c, d_out, "out")))
         return rc;
     if ((rc = set_device(c))) return rc;
@@ -1032,7 +1035,8 @@ int inverse_compact(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offse
         if (P.coef_extent && (e = hipMemsetAsync(c->coef.p, 0, sizeof(float) * P.coef_extent, c->stream)) != hipSuccess)
             return hip_fail(c, e, "memset");
         e = launch_decode_region(c->stream, (const RegionDesc*)d_desc, dtiles, ndt, d_payload, d_offsets, ds.ticket,
-                                 ds.status, (float*)c->coef.p, (uint32_t*)c->errflag.p, ds.ordered, bad, whole);
+                                 ds.status, (float*)c->coef.p, (uint32_t*)c->errflag.p, ds.ordered, bad, whole,
+                                 packed_cap);
         // the units with r == L: their compact units are their cells
         if (e == hipSuccess && any_direct)
             e = launch_corner_box(c->stream, (const RegionDesc*)d_desc, (const FTile*)P.d_ftiles.p,
@@ -1047,6 +1051,9 @@ int inverse_compact(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offse
                        P.ign, P.lds_inverse, P.ifast, P.lds_fast, d_out, bad);
     return e == hipSuccess ? WC_OK : hip_fail(c, e, "inverse launch");
 }
+
+int inverse_dense(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                  const int32_t* levels, float* d_out, const uint64_t* packed_cap);
 
 }  // namespace
 
@@ -1257,8 +1264,20 @@ int wc_inverse_levels(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_off
     if (!d_payload || !d_offsets || !d_out) return fail(c, WC_ERR_INVALID, "null buffer");
     if ((rc = validate_levels(c, units, n, levels))) return rc;
     if (single_level(levels, n)) return wc_inverse(c, d_payload, d_offsets, units, n, d_out);
-    if ((rc = check_aligned(c, d_payload, "payload")) || (rc = check_aligned(c, d_offsets, "offsets", 8)) ||
-        (rc = check_aligned(c, d_out, "out")))
+    return inverse_dense(c, d_payload, d_offsets, units, n, levels, d_out, nullptr);
+}
+
+}  // extern "C"
+
+namespace {
+
+// wc_inverse_levels after its checks, and wc_inverse_packed (packed_cap: d_payload
+// holds packed units, read below *packed_cap; then also for batches of L = 1).
+int inverse_dense(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                  const int32_t* levels, float* d_out, const uint64_t* packed_cap) {
+    int rc;
+    if ((rc = check_aligned(c, d_payload, "payload", packed_cap ? 8 : 16)) ||  // packed: as wc_unpack
+        (rc = check_aligned(c, d_offsets, "offsets", 8)) || (rc = check_aligned(c, d_out, "out")))
         return rc;
     if ((rc = set_device(c))) return rc;
     const bool rows = c->opt_inv_rows;
@@ -1277,9 +1296,13 @@ int wc_inverse_levels(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_off
     uint32_t* bad = (uint32_t*)c->npairs.p;
     {
         StageTimer t(c, WC_STAGE_DECODE);
-        e = launch_decode(c->stream, (const UnitDev*)P.d_units.p, (const FTile*)P.d_dtiles.p, (uint32_t)P.dtiles.size(),
-                          nullptr, 0u, nullptr, 0u, d_payload, d_offsets, ds.ticket, ds.status, (float*)c->coef.p, nullptr,
-                          (uint32_t*)c->errflag.p, ds.ordered, bad, w.levels);
+        e = packed_cap
+                ? launch_decode_packed(c->stream, (const UnitDev*)P.d_units.p, (const FTile*)P.d_dtiles.p,
+                                       (uint32_t)P.dtiles.size(), d_payload, d_offsets, *packed_cap, ds.ticket, ds.status,
+                                       (float*)c->coef.p, (uint32_t*)c->errflag.p, ds.ordered, w.levels, bad)
+                : launch_decode(c->stream, (const UnitDev*)P.d_units.p, (const FTile*)P.d_dtiles.p,
+                                (uint32_t)P.dtiles.size(), nullptr, 0u, nullptr, 0u, d_payload, d_offsets, ds.ticket,
+                                ds.status, (float*)c->coef.p, nullptr, (uint32_t*)c->errflag.p, ds.ordered, bad, w.levels);
         if (e != hipSuccess) return hip_fail(c, e, "decode launch");
     }
     c->err_check_pending = true;  // malformed payloads surface at the next wc_synchronize
@@ -1290,15 +1313,16 @@ int wc_inverse_levels(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_off
     return e == hipSuccess ? WC_OK : hip_fail(c, e, "inverse launch");
 }
 
-// Reduced-resolution inverse: every unit's region is its whole primed box
-// (inverse_compact, wc_region.hip).
-int wc_inverse_coarse(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
-                      const int32_t* levels, const int32_t* reduce, const wc_unit* out_units, float* d_out) {
+// wc_inverse_coarse (packed_cap NULL) and wc_inverse_packed_coarse.
+int inverse_coarse(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                   const int32_t* levels, const int32_t* reduce, const wc_unit* out_units, float* d_out,
+                   const uint64_t* packed_cap) {
     if (!c) return WC_ERR_INVALID;
     int rc;
     if ((rc = validate_units(c, units, n))) return rc;
     if (n == 0) return WC_OK;
     if (!d_payload || !d_offsets || !reduce || !out_units || !d_out) return fail(c, WC_ERR_INVALID, "null buffer");
+    if (packed_cap && (rc = validate_pack(c, units, n))) return rc;
     std::vector<int32_t> ones;
     if (!levels) {
         ones.assign(n, 1);
@@ -1307,7 +1331,8 @@ int wc_inverse_coarse(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_off
     if ((rc = validate_levels(c, units, n, levels)) || (rc = validate_coarse(c, units, n, levels, reduce, out_units)))
         return rc;
     if (std::all_of(reduce, reduce + n, [](int32_t r) { return r == 0; }))
-        return wc_inverse_levels(c, d_payload, d_offsets, out_units, n, levels, d_out);
+        return packed_cap ? inverse_dense(c, d_payload, d_offsets, out_units, n, levels, d_out, packed_cap)
+                          : wc_inverse_levels(c, d_payload, d_offsets, out_units, n, levels, d_out);
     std::vector<RegionDesc>& desc = c->cdesc;
     desc.resize(n);
     for (int u = 0; u < n; ++u) {
@@ -1316,18 +1341,19 @@ int wc_inverse_coarse(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_off
         // valid for odd dimensions (L = 1, r = 0), which region_end is not; 0 for a unit without cells
         if (d.W && d.H && d.D) d.end = (uint32_t)((((uint64_t)d.w - 1) * d.H + ((uint64_t)d.h - 1)) * d.D + d.d);
     }
-    return inverse_compact(c, d_payload, d_offsets, units, n, out_units, d_out, desc, true);
+    return inverse_compact(c, d_payload, d_offsets, units, n, out_units, d_out, desc, true, packed_cap);
 }
 
-// Sub-box inverse (inverse_compact, wc_region.hip).
-int wc_inverse_region(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
-                      const int32_t* levels, const int32_t* reduce, const wc_region* regions, const wc_unit* out_units,
-                      float* d_out) {
+// wc_inverse_region (packed_cap NULL) and wc_inverse_packed_region.
+int inverse_region(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                   const int32_t* levels, const int32_t* reduce, const wc_region* regions, const wc_unit* out_units,
+                   float* d_out, const uint64_t* packed_cap) {
     if (!c) return WC_ERR_INVALID;
     int rc;
     if ((rc = validate_units(c, units, n))) return rc;
     if (n == 0) return WC_OK;
     if (!d_payload || !d_offsets || !regions || !out_units || !d_out) return fail(c, WC_ERR_INVALID, "null buffer");
+    if (packed_cap && (rc = validate_pack(c, units, n))) return rc;
     std::vector<int32_t> ones, zeros;
     if (!levels) {
         ones.assign(n, 1);
@@ -1354,7 +1380,59 @@ int wc_inverse_region(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_off
         d.end = (uint32_t)region_end(d.w, d.h, d.d, d.L, d.ox, d.oy, d.oz, d.sx, d.sy, d.sz, (uint32_t)d.H,
                                      (uint32_t)d.D);  // <= W*H*D < 2^31; 0: a region without cells
     }
-    return inverse_compact(c, d_payload, d_offsets, units, n, out_units, d_out, desc, false);
+    return inverse_compact(c, d_payload, d_offsets, units, n, out_units, d_out, desc, false, packed_cap);
+}
+
+}  // namespace
+
+extern "C" {
+
+// Reduced-resolution inverse: every unit's region is its whole primed box
+// (inverse_compact, wc_region.hip).
+int wc_inverse_coarse(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                      const int32_t* levels, const int32_t* reduce, const wc_unit* out_units, float* d_out) {
+    return inverse_coarse(c, d_payload, d_offsets, units, n, levels, reduce, out_units, d_out, nullptr);
+}
+
+// Sub-box inverse (inverse_compact, wc_region.hip).
+int wc_inverse_region(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                      const int32_t* levels, const int32_t* reduce, const wc_region* regions, const wc_unit* out_units,
+                      float* d_out) {
+    return inverse_region(c, d_payload, d_offsets, units, n, levels, reduce, regions, out_units, d_out, nullptr);
+}
+
+// The decoders over packed units (wc_packsrc.h): wc_unpack followed by
+// wc_inverse_levels / wc_inverse_coarse / wc_inverse_region, bit for bit, without
+// the standard payloads in between.  The full decode takes the dense path for
+// every L (the row-indexed inverse reads pairs at random from a standard payload).
+int wc_inverse_packed(wc_ctx* c, const uint8_t* d_packed, const uint64_t* d_packed_offsets, uint64_t packed_capacity,
+                      const wc_unit* units, int n, const int32_t* levels, float* d_out) {
+    if (!c) return WC_ERR_INVALID;
+    int rc;
+    if ((rc = validate_units(c, units, n))) return rc;
+    if (n == 0) return WC_OK;
+    if (!d_packed || !d_packed_offsets || !d_out) return fail(c, WC_ERR_INVALID, "null buffer");
+    if ((rc = validate_pack(c, units, n))) return rc;
+    std::vector<int32_t> ones;
+    if (!levels) {
+        ones.assign(n, 1);
+        levels = ones.data();
+    }
+    if ((rc = validate_levels(c, units, n, levels))) return rc;
+    return inverse_dense(c, d_packed, d_packed_offsets, units, n, levels, d_out, &packed_capacity);
+}
+
+int wc_inverse_packed_coarse(wc_ctx* c, const uint8_t* d_packed, const uint64_t* d_packed_offsets,
+                             uint64_t packed_capacity, const wc_unit* units, int n, const int32_t* levels,
+                             const int32_t* reduce, const wc_unit* out_units, float* d_out) {
+    return inverse_coarse(c, d_packed, d_packed_offsets, units, n, levels, reduce, out_units, d_out, &packed_capacity);
+}
+
+int wc_inverse_packed_region(wc_ctx* c, const uint8_t* d_packed, const uint64_t* d_packed_offsets,
+                             uint64_t packed_capacity, const wc_unit* units, int n, const int32_t* levels,
+                             const int32_t* reduce, const wc_region* regions, const wc_unit* out_units, float* d_out) {
+    return inverse_region(c, d_packed, d_packed_offsets, units, n, levels, reduce, regions, out_units, d_out,
+                          &packed_capacity);
 }
 
 int wc_rmse(wc_ctx* c, const void* d_orig, int dtype, const float* d_regen, const wc_unit* units, int n,

@@ -73,6 +73,10 @@ hipError_t launch_decode(hipStream_t, const UnitDev*, const FTile*, uint32_t, co
                          unsigned long long*, uint32_t, const uint8_t*, const uint64_t*, uint32_t*,
                          unsigned long long*, float*, uint2*, uint32_t*, int, uint32_t*,
                          const int32_t* levels = nullptr);
+// the dense decode of every unit from packed units, read below cap (wc_inverse_packed)
+hipError_t launch_decode_packed(hipStream_t, const UnitDev*, const FTile*, uint32_t nft, const uint8_t* packed,
+                                const uint64_t* offsets, uint64_t cap, uint32_t* ticket, unsigned long long* status,
+                                float* flat, uint32_t* err, int ordered, const int32_t* levels, uint32_t* bad);
 hipError_t launch_pair_counts(hipStream_t, const UnitDev*, int, const uint8_t*, const uint64_t*, uint32_t*, uint32_t*);
 hipError_t launch_inverse_rows(hipStream_t, const RTile*, uint32_t, size_t, uint32_t, const uint8_t*,
                                const uint64_t*, const uint2*, float*, int, const void*, int, const UnitDev*, int,
@@ -116,7 +120,7 @@ hipError_t launch_budget(hipStream_t, const UnitDev*, int, const LtUnit*, const 
 hipError_t launch_decode_region(hipStream_t, const RegionDesc*, const FTile* dtiles, uint32_t ndt,
                                 const uint8_t* payload, const uint64_t* offsets, uint32_t* ticket,
                                 unsigned long long* status, float* compact, uint32_t* err, int ordered, uint32_t* bad,
-                                bool whole);
+                                bool whole, const uint64_t* packed_cap = nullptr);
 hipError_t launch_corner_box(hipStream_t, const RegionDesc*, const FTile* ftiles, uint32_t nft, const float* compact,
                              float* out, const uint32_t* bad);
 
@@ -326,6 +330,9 @@ int validate_region(wc_ctx* c, const wc_unit* units, int n, const int32_t* level
 int inverse_compact_host(wc_ctx* c, const uint8_t* payload, const uint64_t* offsets, const wc_unit* units, int n,
                          const int32_t* levels, const int32_t* reduce, const wc_region* regions,
                          const wc_unit* out_units, float* out);
+
+// wc_packhost.cpp: no unit above WC_PACK_MAX_CELLS (the device calls over packed units)
+int validate_pack(wc_ctx* c, const wc_unit* units, int n);
 
 // Bracket one launch with events when profiling is on.
 struct StageTimer {

@@ -7,6 +7,7 @@
 //   K7   k_rmse_*: per-unit RMSE                      src/calc-loss.cpp:12-43
 // The inverse pair `avg +/- diff` is evaluated in double and stored as float
 // by the reference; a float add is bit-identical (53 >= 2*24 + 2).
+#include "wc_packsrc.h"
 #include "wc_pairscan.h"
 #include "wc_xform.h"
 
@@ -92,8 +93,8 @@ __global__ __launch_bounds__(kThreads, WC_RIX_MINB) void k_rowindex(const UnitDe
     Scan::WaveSums ws;
 #pragma unroll
     for (int r = 0; r < kRixRounds5; ++r) s_v[r][tid] = ws.round(v[r], kw + r * 64 + l, n);
-    const Scan::Prefix P = Scan::prefix(ws.finish(err), t, n, runs, status + U.dt_begin, GranuleEpoch32{epoch & kEpochMask},
-                                        err, s_w, s_x, w, l);
+    const Scan::Prefix P = Scan::prefix(ws.finish(err), t, n, PayloadRuns{runs}, status + U.dt_begin,
+                                        GranuleEpoch32{epoch & kEpochMask}, err, s_w, s_x, w, l);
     const uint32_t nc = (uint32_t)U.ncells;
     const uint32_t A = sat_add(P.excl, P.wexcl);
 
@@ -127,10 +128,12 @@ __global__ __launch_bounds__(kThreads, WC_RIX_MINB) void k_rowindex(const UnitDe
 // L >= 2).  A unit whose header disagrees is left alone: nothing past the
 // header is read, nothing is decoded, kErrHeader is raised and bad[u] tells the
 // level passes and the one-level inverse (later launches) to skip the unit.
-template <bool LV>
+// Src: the pairs' source, a standard payload at payload + offsets[u]
+// (PayloadPairs) or a packed unit there (PackedPairs, wc_packsrc.h: payload is
+// then the packed buffer and its capacity; wc_inverse_packed, LV only).
+template <bool LV, class Src = PayloadPairs>
 __global__ __launch_bounds__(kThreads) void k_decode(const UnitDev* __restrict__ units,
-                                                   const FTile* __restrict__ tiles,
-                                                   const uint8_t* __restrict__ payload,
+                                                   const FTile* __restrict__ tiles, typename Src::Arg payload,
                                                    const uint64_t* __restrict__ offsets, uint32_t* __restrict__ ticket,
                                                    unsigned long long* __restrict__ status, float* __restrict__ flat,
                                                    uint32_t* __restrict__ err, int ordered,
@@ -139,14 +142,20 @@ __global__ __launch_bounds__(kThreads) void k_decode(const UnitDev* __restrict__
     using Scan = PairScan<Exact64, Granule62, kFlatTile, LoadPairs>;
     __shared__ Scan::T s_w[4];
     __shared__ Scan::V s_x[2];
+    typename Src::Lds* s_src = nullptr;
+    if constexpr (Src::kLds) {
+        __shared__ typename Src::Lds s_own;
+        s_src = &s_own;
+    }
+    Src src(payload, err);
     const int tid = threadIdx.x, l = tid & 63, w = tid >> 6;
     const FTile ft = tiles[blockIdx.x];
     const uint32_t u = ft.unit;
     const UnitDev& U = units[u];
-    const uint8_t* ph = payload + offsets[u];
+    const uint64_t off = offsets[u];
     int32_t nrle;
     const int32_t want = LV && levels[u] >= 2 ? -levels[u] : (int32_t)U.ncells;
-    const bool hok = header_ok(U.nx, U.ny, U.nz, want, ph, nrle);
+    const bool hok = src.open(off, U.nx, U.ny, U.nz, want, nrle);
     if constexpr (LV) {
         if (ft.index == 0 && tid == 0) {
             bad[u] = hok ? kUnitRun : kUnitRefused;
@@ -168,16 +177,19 @@ __global__ __launch_bounds__(kThreads) void k_decode(const UnitDev* __restrict__
 
     // 1. this lane's pairs and their in-wave inclusive sums of (run + 1);
     // 2. start of this tile's range: the sum over the unit's earlier tiles
-    const uint32_t* __restrict__ runs = reinterpret_cast<const uint32_t*>(ph + 20);
+    src.enter(t, s_src, w, l);
     const int64_t kw = Scan::wave_first(t, w);
     uint2 q[Scan::kRounds];
 #pragma unroll
-    for (int r = 0; r < Scan::kRounds; ++r) q[r] = Scan::load(runs, kw + r * 64 + l, n);
+    for (int r = 0; r < Scan::kRounds; ++r) q[r] = src.fetch(r, kw + r * 64 + l, n, w, l);
+#pragma unroll
+    for (int r = 0; r < Scan::kRounds; ++r) q[r] = src.unpack(r, q[r], w, l);
     uint64_t incl[Scan::kRounds];
     Scan::WaveSums ws;
 #pragma unroll
-    for (int r = 0; r < Scan::kRounds; ++r) incl[r] = ws.round(q[r], kw + r * 64 + l, n);
-    const Scan::Prefix P = Scan::prefix(ws.finish(err), t, n, runs, status + U.dt_begin, Granule62{}, err, s_w, s_x, w, l);
+    for (int r = 0; r < Scan::kRounds; ++r) incl[r] = ws.round(q[r], kw + r * 64 + l, src.lim(r, n));
+    const Scan::Prefix P = Scan::prefix(ws.finish(err), t, n, src, status + U.dt_begin,
+                                        Granule62{}, err, s_w, s_x, w, l);
     const uint64_t nc = U.ncells;
     const uint64_t A = P.excl;
     const uint64_t Ac = A < nc ? A : nc;
@@ -194,7 +206,7 @@ __global__ __launch_bounds__(kThreads) void k_decode(const UnitDev* __restrict__
         for (int r = 0; r < Scan::kRounds; ++r) {
             const int64_t k = kw + r * 64 + l;
             const uint64_t o = base + incl[r] - c0;
-            if (k < n && o < (uint64_t)kDecChunk) buf[o] = __uint_as_float(q[r].y);
+            if (k < src.lim(r, n) && o < (uint64_t)kDecChunk) buf[o] = __uint_as_float(q[r].y);
         }
         __syncthreads();
         for (int i = tid; i < kDecChunk / 4; i += kThreads) {
@@ -995,6 +1007,18 @@ hipError_t launch_decode(hipStream_t st, const UnitDev* units, const FTile* ftil
     if (nft && levels)
         k_decode<true><<<nft, kThreads, 0, st>>>(units, ftiles, payload, offsets, ticket, status, flat, err, ordered,
                                                  levels, npairs);
+    return hipGetLastError();
+}
+
+// K5 of wc_inverse_packed: every unit decodes densely, from its packed unit
+// (zeroed ticket / status; bad: the per-unit "header disagrees" words).
+hipError_t launch_decode_packed(hipStream_t st, const UnitDev* units, const FTile* ftiles, uint32_t nft,
+                                const uint8_t* packed, const uint64_t* offsets, uint64_t cap, uint32_t* ticket,
+                                unsigned long long* status, float* flat, uint32_t* err, int ordered,
+                                const int32_t* levels, uint32_t* bad) {
+    if (nft)
+        k_decode<true, PackedPairs><<<nft, kThreads, 0, st>>>(units, ftiles, PackedPairs::Arg{packed, cap}, offsets, ticket,
+                                                              status, flat, err, ordered, levels, bad);
     return hipGetLastError();
 }
 

@@ -34,24 +34,13 @@
 // before or inside a tile refuses the tile, and a chunk is read only if its end,
 // from the table sum, lies below packed_capacity.  Pairs go to 20 + 8 k of the
 // unit's forward slot with k < nrle <= cells.  All refusals raise kErrHeader.
-#include "wc_device.h"
-#include "wc_packfmt.h"
+#include "wc_packsrc.h"
 
 namespace wc {
 
 constexpr int kPackChunks = kPackTile / 64;          // chunks per tile
 constexpr int kPackWaveChunks = kPackChunks / 4;     // chunks per wave
 static_assert(kPackWaveChunks == 8, "a wave's table bytes are one aligned 8-byte group");
-
-__device__ __forceinline__ uint32_t wave_or_u32_u(uint32_t v) {
-    v |= dpp_u32<0x111, 0xf>(v);
-    v |= dpp_u32<0x112, 0xf>(v);
-    v |= dpp_u32<0x114, 0xf>(v);
-    v |= dpp_u32<0x118, 0xf>(v);
-    v |= dpp_u32<0x142, 0xa>(v);
-    v |= dpp_u32<0x143, 0xc>(v);
-    return __builtin_amdgcn_readlane(v, 63);
-}
 
 // The source unit's header: a standard or multi-level header of the unit with
 // 0 <= nrle <= cells.
@@ -61,29 +50,6 @@ __device__ __forceinline__ bool source_ok(const PackDesc& C, const uint8_t* __re
     nrle = h[4];
     return h[0] == C.W && h[1] == C.H && h[2] == C.D && pack_header(C.W, C.H, C.D, h[3], L, V) && V == 0 &&
            nrle >= 0 && (uint32_t)nrle <= C.ncells;
-}
-
-// Sum of the table bytes of the `words` 8-byte groups at `table` (8-B aligned),
-// over the block; bad: some byte was above 31.  s: 8 words of LDS.
-__device__ __forceinline__ uint32_t block_table_sum(const uint8_t* __restrict__ table, uint32_t words, uint32_t& bad,
-                                                    uint32_t* s, int w, int l) {
-    const unsigned long long* __restrict__ t = reinterpret_cast<const unsigned long long*>(table);
-    uint32_t acc = 0, hi = 0;
-    for (uint32_t i = threadIdx.x; i < words; i += kThreads) {
-        const unsigned long long x = t[i];
-        acc = __builtin_amdgcn_sad_u8((uint32_t)x, 0u, acc);
-        acc = __builtin_amdgcn_sad_u8((uint32_t)(x >> 32), 0u, acc);
-        hi |= (x & 0xE0E0E0E0E0E0E0E0ull) ? 1u : 0u;
-    }
-    acc = wave_sum_u32_u(acc);
-    hi = wave_or_u32_u(hi);
-    if (l == 0) {
-        s[w] = acc;
-        s[4 + w] = hi;
-    }
-    __syncthreads();
-    bad = s[4] | s[5] | s[6] | s[7];
-    return s[0] + s[1] + s[2] + s[3];
 }
 
 // Blocks past the unit's ceil(n / kPackTile) tiles exit after reading the header.

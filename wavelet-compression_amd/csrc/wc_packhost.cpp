@@ -26,7 +26,7 @@ hipError_t launch_dense(hipStream_t, bool standard, int n, const uint64_t* bytes
                         const uint64_t* src_off, const uint8_t* src, uint64_t* dense, uint8_t* dst);
 }
 
-namespace {
+namespace wc {
 
 int validate_pack(wc_ctx* c, const wc_unit* units, int n) {
     for (int i = 0; i < n; ++i)
@@ -36,6 +36,10 @@ int validate_pack(wc_ctx* c, const wc_unit* units, int n) {
                         "unit's width table per tile)");
     return WC_OK;
 }
+
+}  // namespace wc
+
+namespace {
 
 // The batch's descriptors on the device (c->pk_desc: PackDesc[n] | FTile[pk_ntiles]).
 int pack_plan(wc_ctx* c, const wc_unit* units, int n, int vbytes) {

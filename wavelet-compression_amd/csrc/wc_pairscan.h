@@ -80,6 +80,8 @@ struct Sat32 {
     static __device__ __forceinline__ T add(T a, T b) { return sat_add(a, b); }
     static __device__ __forceinline__ T wave_incl(T v) { return wave_incl_sum32_sat(v); }
     static __device__ __forceinline__ T last(T s) { return __builtin_amdgcn_readlane(s, 63); }
+    // an exact sum of terms (a packed chunk's, wc_packsrc.h) as the saturating adds would leave it
+    static __device__ __forceinline__ T from64(uint64_t x) { return x > 0xffffffffull ? 0xffffffffu : (T)x; }
 };
 struct Exact64 {
     using T = uint64_t;
@@ -102,6 +104,7 @@ struct Exact64 {
         const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(s >> 32), 63);
         return ((uint64_t)hi << 32) | lo;
     }
+    static __device__ __forceinline__ T from64(uint64_t x) { return x; }
 };
 
 // What a lane keeps of a pair: the run alone (the values stay in the payload;
@@ -124,6 +127,50 @@ struct LoadPairs {
     }
     static __device__ __forceinline__ E none() { return make_uint2(0u, 0u); }
     static __device__ __forceinline__ int32_t run(E e) { return (int32_t)e.x; }
+};
+
+// Where k_decode and k_decode_region take a unit's pairs from: a standard
+// payload (here) or a packed unit (wc_packsrc.h PackedPairs).  open(): the
+// unit's header at its offset, against the box and the standard ncoeff field
+// `want`; enter(): once per block, after the tile index is known; fetch(): round
+// r's load for this lane, pair k of n, and unpack(): the pair from it (the loads
+// of all rounds are issued before the first is used); lim(): the pair count that round's tests
+// of k < n use (a packed chunk that was refused holds no pair); tile_sum(): the
+// look-back's derive path, the sum of run + 1 over tile j of the unit's n pairs by
+// one wave, as tile j's own block publishes it.
+struct PayloadRuns {  // the derive path alone (k_rowindex)
+    const uint32_t* __restrict__ runs = nullptr;
+    template <class S, int TILE>
+    __device__ __forceinline__ typename S::T tile_sum(int64_t j, typename S::K n, int l) const {
+        using K = typename S::K;
+        const K k0 = (K)j * TILE, k1 = min(k0 + (K)TILE, n);
+        typename S::T a = 0;
+        for (K k = k0 + (K)l; k < k1; k += 64) a = S::add(a, S::term((int32_t)runs[2 * k]));
+        return S::last(S::wave_incl(a));
+    }
+};
+struct PayloadPairs : PayloadRuns {
+    using Arg = const uint8_t* __restrict__;  // the kernel argument: the payload buffer
+    static constexpr bool kLds = false;
+    struct Lds;  // none
+    const uint8_t* __restrict__ payload;
+    __device__ __forceinline__ PayloadPairs(Arg p, uint32_t*) : payload(p) {}
+    __device__ __forceinline__ bool open(uint64_t off, const int32_t& W, const int32_t& H, const int32_t& D,
+                                         int32_t want, int32_t& nrle) {
+        const uint8_t* ph = payload + off;
+        runs = reinterpret_cast<const uint32_t*>(ph + 20);
+        return header_ok(W, H, D, want, ph, nrle);
+    }
+    __device__ __forceinline__ void enter(uint32_t, Lds*, int, int) {}
+    template <class K>
+    __device__ __forceinline__ uint2 fetch(int, K k, K n, int, int) const {
+        return k < n ? LoadPairs::load(runs, k) : LoadPairs::none();
+    }
+    __device__ __forceinline__ uint2 unpack(int, uint2 q, int, int) const { return q; }
+    template <class K>
+    __device__ __forceinline__ K lim(int, K n) const {
+        return n;
+    }
 };
 
 // The scan of one pair tile, from the tile index to the exclusive prefix known
@@ -193,10 +240,11 @@ struct PairScan {
 
     // The four waves' sums through s_w; wave 0 publishes the tile's aggregate
     // at st[t], looks back over st[0..t) and publishes the inclusive prefix;
-    // the result reaches every wave through s_x[1].
-    static __device__ __forceinline__ Prefix prefix(T wsum, uint32_t t, K n, const uint32_t* __restrict__ runs,
-                                                    unsigned long long* st, G g, uint32_t* __restrict__ err, T* s_w,
-                                                    V* s_x, int w, int l) {
+    // the result reaches every wave through s_x[1].  src: the source of the
+    // unit's n pairs (PayloadRuns, PayloadPairs, or PackedPairs of wc_packsrc.h).
+    template <class Src>
+    static __device__ __forceinline__ Prefix prefix(T wsum, uint32_t t, K n, const Src& src, unsigned long long* st,
+                                                    G g, uint32_t* __restrict__ err, T* s_w, V* s_x, int w, int l) {
         if (l == 0) s_w[w] = wsum;
         __syncthreads();
         Prefix P{0, 0, 0};
@@ -212,12 +260,8 @@ struct PairScan {
             } else {
                 if (l == 0) st_rlx(st + t, g.encode(kFlagAgg, P.tot));
                 // a predecessor tile unpublished after the wait bound: its sum from its pairs
-                excl = lookback_sum(st, (int64_t)t, l, err, g, [&](int64_t j) -> T {
-                    const K k0 = (K)j * TILE, k1 = min(k0 + (K)TILE, n);
-                    T a = 0;
-                    for (K k = k0 + (K)l; k < k1; k += 64) a = S::add(a, S::term((int32_t)runs[2 * k]));
-                    return S::last(S::wave_incl(a));
-                });
+                excl = lookback_sum(st, (int64_t)t, l, err, g,
+                                    [&](int64_t j) -> T { return src.template tile_sum<S, TILE>(j, n, l); });
                 if (l == 0) st_rlx(st + t, g.encode(kFlagIncl, G::add(excl, P.tot)));
             }
             if (l == 0) s_x[1] = excl;

@@ -56,6 +56,7 @@
 // is < s of that axis (wc_regionmap.h).  Either way every store is inside the
 // compact unit, whatever the payload holds; pair loads are bounded by the
 // header's pair count, as in k_decode.
+#include "wc_packsrc.h"
 #include "wc_pairscan.h"
 #include "wc_regionmap.h"
 
@@ -69,10 +70,13 @@ namespace wc {
 // nothing past the header is read, no cell is written, every later launch skips
 // the unit); kUnitBox = r == L (k_corner_box writes the cells, the level passes
 // and the inverse skip the unit); kUnitRun otherwise.
-template <bool kWhole>
+// Src: the pairs' source, a standard payload at payload + offsets[u]
+// (PayloadPairs) or a packed unit there (PackedPairs, wc_packsrc.h: payload is
+// then the packed buffer and its capacity; wc_inverse_packed_coarse / _region).
+template <bool kWhole, class Src = PayloadPairs>
 __global__ __launch_bounds__(kThreads) void k_decode_region(const RegionDesc* __restrict__ desc,
                                                           const FTile* __restrict__ tiles,
-                                                          const uint8_t* __restrict__ payload,
+                                                          typename Src::Arg payload,
                                                           const uint64_t* __restrict__ offsets,
                                                           uint32_t* __restrict__ ticket,
                                                           unsigned long long* __restrict__ status,
@@ -82,6 +86,12 @@ __global__ __launch_bounds__(kThreads) void k_decode_region(const RegionDesc* __
     using Scan = PairScan<Sat32, Granule62, kFlatTile, LoadPairs>;
     __shared__ Scan::T s_w[4];
     __shared__ Scan::V s_x[2];
+    typename Src::Lds* s_src = nullptr;
+    if constexpr (Src::kLds) {
+        __shared__ typename Src::Lds s_own;
+        s_src = &s_own;
+    }
+    Src src(payload, err);
     const int tid = threadIdx.x, l = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const FTile ft = tiles[blockIdx.x];
@@ -96,9 +106,8 @@ __global__ __launch_bounds__(kThreads) void k_decode_region(const RegionDesc* __
     const uint64_t poff = offsets[u];
     asm volatile("" ::"s"(poff), "s"(C.W));
     if (kWhole ? __builtin_expect(none, false) : none) return;
-    const uint8_t* ph = payload + poff;
     int32_t nrle;
-    const bool hok = header_ok(C.W, C.H, C.D, C.want, ph, nrle);
+    const bool hok = src.open(poff, C.W, C.H, C.D, C.want, nrle);
     if (ft.index == 0 && tid == 0) {
         bad[u] = !hok ? kUnitRefused : C.direct ? kUnitBox : kUnitRun;
         if (!hok) atomicOr(err, kErrHeader);
@@ -112,16 +121,19 @@ __global__ __launch_bounds__(kThreads) void k_decode_region(const RegionDesc* __
 
     // 1. this lane's pairs and the saturating in-wave inclusive sums of (run + 1);
     // 2. the sum over the unit's earlier tiles
-    const uint32_t* __restrict__ runs = reinterpret_cast<const uint32_t*>(ph + 20);
+    src.enter(t, s_src, w, l);
     const uint32_t kw = Scan::wave_first(t, w);
     uint2 q[Scan::kRounds];
 #pragma unroll
-    for (int r = 0; r < Scan::kRounds; ++r) q[r] = Scan::load(runs, kw + r * 64 + l, n);
+    for (int r = 0; r < Scan::kRounds; ++r) q[r] = src.fetch(r, kw + r * 64 + l, n, w, l);
+#pragma unroll
+    for (int r = 0; r < Scan::kRounds; ++r) q[r] = src.unpack(r, q[r], w, l);
     uint32_t incl[Scan::kRounds];
     Scan::WaveSums ws;
 #pragma unroll
-    for (int r = 0; r < Scan::kRounds; ++r) incl[r] = ws.round(q[r], kw + r * 64 + l, n);
-    const Scan::Prefix P = Scan::prefix(ws.finish(err), t, n, runs, status + C.dt_begin, Granule62{}, err, s_w, s_x, w, l);
+    for (int r = 0; r < Scan::kRounds; ++r) incl[r] = ws.round(q[r], kw + r * 64 + l, src.lim(r, n));
+    const Scan::Prefix P = Scan::prefix(ws.finish(err), t, n, src, status + C.dt_begin,
+                                        Granule62{}, err, s_w, s_x, w, l);
     const uint64_t A = P.excl;  // positions before this tile's first pair
     if (A >= (uint64_t)C.end) return;  // uniform: the whole tile is past the last needed pair (its sum is published)
 
@@ -132,7 +144,7 @@ __global__ __launch_bounds__(kThreads) void k_decode_region(const RegionDesc* __
     for (int r = 0; r < Scan::kRounds; ++r) {
         const uint32_t k = kw + r * 64 + l;
         const uint64_t p64 = base + incl[r] - 1u;  // incl >= 1 where k < n
-        if (k >= n || p64 >= (uint64_t)C.end) continue;
+        if (k >= src.lim(r, n) || p64 >= (uint64_t)C.end) continue;
         const uint32_t p = (uint32_t)p64;  // < end <= W*H*D < 2^31
         const uint32_t row = div_rows(p, C.dmagic), K = p - row * (uint32_t)C.D;
         const uint32_t I = div_rows(row, C.hmagic), J = row - I * (uint32_t)C.H;
@@ -192,8 +204,11 @@ __global__ __launch_bounds__(kThreads) void k_corner_box(const RegionDesc* __res
 hipError_t launch_decode_region(hipStream_t st, const RegionDesc* desc, const FTile* dtiles, uint32_t ndt,
                                 const uint8_t* payload, const uint64_t* offsets, uint32_t* ticket,
                                 unsigned long long* status, float* compact, uint32_t* err, int ordered, uint32_t* bad,
-                                bool whole) {
-    if (ndt)
+                                bool whole, const uint64_t* packed_cap) {
+    if (ndt && packed_cap)  // the payload is packed units, read below *packed_cap
+        (whole ? k_decode_region<true, PackedPairs> : k_decode_region<false, PackedPairs>)<<<ndt, kThreads, 0, st>>>(
+            desc, dtiles, PackedPairs::Arg{payload, *packed_cap}, offsets, ticket, status, compact, err, ordered, bad);
+    else if (ndt)
         (whole ? k_decode_region<true> : k_decode_region<false>)<<<ndt, kThreads, 0, st>>>(
             desc, dtiles, payload, offsets, ticket, status, compact, err, ordered, bad);
     return hipGetLastError();
