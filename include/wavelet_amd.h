@@ -537,6 +537,76 @@ int wc_forward_levels_budget_host(wc_ctx* ctx, const void* cells, int dtype, con
                                   uint64_t payload_capacity, uint64_t* offsets, uint32_t* kept, float* thresh,
                                   uint32_t* key, double* rmse);
 
+/* Opt-in thinning in the compressed domain (not in the reference): a standard
+ * payload becomes a smaller one under a tighter pair budget or under per-level
+ * thresholds, without its cells or its dense coefficients ever existing.  The
+ * work follows the payload's pairs, not the box.
+ *
+ * The rule.  P is a standard payload of a unit W x H x D with L levels (L from
+ * its header, as wc_payload_levels), N = W*H*D.  A(P) is the dense flat array
+ * rle_decode gives: pair k sits at p_k = sum_{j<=k}(run_j + 1) - 1, a pair whose
+ * position reaches N is dropped, everything else is 0.0f.
+ *   thin_budget(P, K) = the bytes wc_forward_levels_budget's selection and emit
+ *     give on A(P): candidates 1 <= m <= 0x7F800000, key = m + ((WC_LTOL_SHIFT *
+ *     (lvl - 1)) << WC_HIST_SHIFT), T = the (K + 1)-th largest key or 0 with at
+ *     most K candidates, kept = key > T (ties at T are all dropped), the header of
+ *     wc_forward_levels and the reference's run rule on the kept set.
+ *   thin_thresh(P, t_1..t_L) keeps exactly the entries with |c| > t_lvl (strict:
+ *     NaN is never kept).  Each t_l is a float >= 0, +inf allowed; a NaN or
+ *     negative threshold is WC_ERR_INVALID.
+ * Consequences: a pair with value +-0 or NaN, or past N, is never in the output;
+ * kept <= min(K, pairs); the output is never longer than the input; thinning is
+ * idempotent at the same K or thresholds; thinning a thresh = t0 payload at
+ * per-level thresholds all equal to t1 >= t0 gives the bytes of wc_forward_levels
+ * with the explicit threshold t1; thinning a thresh = 0.0f payload with budget K
+ * gives the bytes of wc_forward_levels_budget with K whenever the payload holds
+ * every candidate.  Unit shapes: those wc_forward_levels accepts.  A packed unit
+ * is refused (WC_ERR_FORMAT): wc_unpack first.
+ *
+ *   wc_thin_unit: host-only, no device; the rule on one payload of `len` bytes.
+ *     Exactly one of max_pairs (K) and thresh (levels floats) is non-NULL.  out
+ *     receives at most `cap` bytes, *written their count.  key (T; 0 for the
+ *     threshold form) and thresh_out (levels floats) are nullable.  A header that
+ *     is not a standard one, or a negative run: WC_ERR_FORMAT, nothing written.
+ *   wc_thin_bound: the output extent of the device forms.  Unit u's slot is the
+ *     prefix, starting at 4, of 24 + 8 * cap_u; cap_u = min(max_pairs[u], N_u), or
+ *     N_u with max_pairs NULL (the threshold form: wc_payload_bound).
+ *   wc_thin_budget / wc_thin_thresh: payloads at d_payload + d_offsets[u]
+ *     (multiples of 4) -> slots in d_out (16-B aligned).  levels, max_pairs and
+ *     thresh (n x WC_MAX_LEVELS, unit u's level l at u*WC_MAX_LEVELS + l - 1):
+ *     HOST, consumed before the call returns.  d_out_offsets (n + 1; [n] = the end
+ *     of the last unit's bytes), d_kept (n): device.  d_thresh and d_key: device,
+ *     nullable, as in wc_forward_levels_budget.  Asynchronous on the context's
+ *     stream; nothing is read back between the passes; nothing is left staged.
+ *     out_capacity < wc_thin_bound, or d_payload inside the output's extent:
+ *     WC_ERR_INVALID.  The outputs must not overlap the input.
+ *     A header that disagrees with the unit (box, levels, a packed tag) raises
+ *     WC_ERR_FORMAT at the next wc_synchronize; that unit's slot stays untouched
+ *     and its d_kept is 0; the other units are thinned.  A negative run raises
+ *     the same error; that unit's output is unspecified but inside its slot.
+ *     Scratch of the context: 12 B per coefficient the units can hold, rounded up
+ *     to tiles of 4096 (the pair count of a payload is not known to the host).
+ *   wc_thin_budget_host / wc_thin_thresh_host: host buffers; the results packed
+ *     densely as wc_forward_host's (out_capacity >= wc_thin_bound(units, n,
+ *     max_pairs); out_offsets n + 1).  levels NULL reads the headers.  A header
+ *     that disagrees fails the call (WC_ERR_FORMAT) before anything runs.  The
+ *     unit runs (WC_OPT_HOST_CHUNK) go one after another. */
+int wc_thin_unit(const uint8_t* payload, size_t len, const uint32_t* max_pairs, const float* thresh, uint8_t* out,
+                 size_t cap, size_t* written, uint32_t* key, float* thresh_out);
+uint64_t wc_thin_bound(const wc_unit* units, int n, const uint32_t* max_pairs);
+int wc_thin_budget(wc_ctx* ctx, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                   const int32_t* levels, const uint32_t* max_pairs, uint8_t* d_out, uint64_t out_capacity,
+                   uint64_t* d_out_offsets, uint32_t* d_kept, float* d_thresh, uint32_t* d_key);
+int wc_thin_thresh(wc_ctx* ctx, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                   const int32_t* levels, const float* thresh, uint8_t* d_out, uint64_t out_capacity,
+                   uint64_t* d_out_offsets, uint32_t* d_kept);
+int wc_thin_budget_host(wc_ctx* ctx, const uint8_t* payload, const uint64_t* offsets, const wc_unit* units, int n,
+                        const int32_t* levels, const uint32_t* max_pairs, uint8_t* out, uint64_t out_capacity,
+                        uint64_t* out_offsets, uint32_t* kept, float* thresh, uint32_t* key);
+int wc_thin_thresh_host(wc_ctx* ctx, const uint8_t* payload, const uint64_t* offsets, const wc_unit* units, int n,
+                        const int32_t* levels, const float* thresh, uint8_t* out, uint64_t out_capacity,
+                        uint64_t* out_offsets, uint32_t* kept);
+
 /* Opt-in reduced-resolution decode (not in the reference): the box at 1/2^r
  * resolution straight from a payload, without the work of the full resolution.
  * The low-pass corner of the coefficient array after undoing levels L..r+1 is
@@ -933,7 +1003,7 @@ int wc_decompose_host(wc_ctx* ctx, const void* cells, int dtype, const wc_unit* 
 #define WC_STAGE_PAIRS 6      /* header check + pair counts of wc_inverse_rows with a caller row index */
 #define WC_STAGE_TOL 7        /* per-unit bins + threshold pick of the RMSE-tolerance mode (wc_forward_tol); per-level bins, pick
                                  and mask pass of wc_forward_levels_tol; radix select and mask pass of
-                                 wc_forward_levels_budget */
+                                 wc_forward_levels_budget; every pass of wc_thin_budget / wc_thin_thresh */
 #define WC_STAGE_LEVELS 8    /* level passes, key pass and header patch of the multi-level mode (wc_forward_levels,
                                  wc_inverse_levels) */
 #define WC_STAGE_PACK 9      /* packed payloads: k_pack_widths + k_pack_body (wc_pack), k_unpack (wc_unpack) */

@@ -71,6 +71,20 @@ std::vector<CompressedWavelet> compress_rmse(multiBox3D& box, std::vector<int> c
 std::vector<CompressedWavelet> compress_budget(multiBox3D& box, std::vector<int> components, int levels, double ratio,
                                                int time, int level, int box_index, std::string compressed_dir);
 
+// Compressed structs thinned in the compressed domain (GPU, wc_thin_budget_host /
+// wc_thin_thresh_host; not in the reference): what compress_budget's selection at
+// `ratio`, or the test |c| > thresh on every level, leaves of the array each struct
+// decodes to, without its cells or dense coefficients in between.  thin_budget's
+// pair budget is compress_budget's: (max(20, floor(4 N / ratio)) - 20) / 8 for a
+// component of N cells; ties at the boundary are all dropped.  A struct made with
+// thresh = 0 (or a generous budget) thinned at `ratio` is byte for byte what
+// compress_budget gives at `ratio` whenever it holds every candidate.  The levels come
+// from coeff_shape (the header's ncoeff field).  Nothing is written to disk.  A
+// non-positive ratio, or a NaN or negative thresh, exits with a message, as the other
+// errors do.
+std::vector<CompressedWavelet> thin_budget(const std::vector<CompressedWavelet>& compressed, double ratio);
+std::vector<CompressedWavelet> thin_thresh(const std::vector<CompressedWavelet>& compressed, float thresh);
+
 // compress() whose files hold packed units (GPU, wc_pack_host after the forward; not
 // a reference format, include/wavelet_amd.h "Opt-in packed payloads"): each kept
 // value stored in its top `vbytes` bytes (4: lossless; 3, 2: rounded to nearest even,

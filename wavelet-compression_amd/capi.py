@@ -41,6 +41,7 @@ EXPORTED = (
     "wc_packed_bound", "wc_pack", "wc_unpack", "wc_pack_host", "wc_unpack_host",
     "wc_inverse_packed", "wc_inverse_packed_coarse", "wc_inverse_packed_region",
     "wc_inverse_packed_host", "wc_inverse_packed_coarse_host", "wc_inverse_packed_region_host",
+    "wc_thin_unit", "wc_thin_bound", "wc_thin_budget", "wc_thin_thresh", "wc_thin_budget_host", "wc_thin_thresh_host",
 )
 WC_MAX_LEVELS = 4  # levels of the opt-in multi-level transform (1 = the reference's codec)
 WC_PACK_MAX_CELLS = 1 << 21  # the largest unit wc_pack / wc_unpack take (the host rule has no limit)
@@ -184,6 +185,13 @@ def load_library() -> ctypes.CDLL:
         "wc_inverse_packed_host": (i32, [vp, vp, vp, up, i32, vp, vp]),
         "wc_inverse_packed_coarse_host": (i32, [vp, vp, vp, up, i32, vp, vp, up, vp]),
         "wc_inverse_packed_region_host": (i32, [vp, vp, vp, up, i32, vp, vp, rp, up, vp]),
+        "wc_thin_unit": (i32, [vp, ctypes.c_size_t, vp, vp, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
+                               ctypes.POINTER(ctypes.c_uint32), vp]),
+        "wc_thin_bound": (u64, [up, i32, vp]),
+        "wc_thin_budget": (i32, [vp, vp, vp, up, i32, vp, vp, vp, u64, vp, vp, vp, vp]),
+        "wc_thin_thresh": (i32, [vp, vp, vp, up, i32, vp, vp, vp, u64, vp, vp]),
+        "wc_thin_budget_host": (i32, [vp, vp, vp, up, i32, vp, vp, vp, u64, vp, vp, vp, vp]),
+        "wc_thin_thresh_host": (i32, [vp, vp, vp, up, i32, vp, vp, vp, u64, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -398,6 +406,28 @@ class Context:
                                                      ctypes.c_void_p(d_payload), capacity, ctypes.c_void_p(d_offsets),
                                                      ctypes.c_void_p(d_kept), ctypes.c_void_p(d_thresh or 0),
                                                      ctypes.c_void_p(d_key or 0)))
+
+    def thin_budget(self, d_payload: int, d_offsets: int, units, n: int, levels, max_pairs, d_out: int,
+                    capacity: int, d_out_offsets: int, d_kept: int, d_thresh: int | None = None,
+                    d_key: int | None = None):
+        """wc_thin_budget: standard payloads -> the payloads of a tighter pair budget, in
+        the compressed domain.  Slots of 24 + 8 min(max_pairs, N) bytes (thin_bound)."""
+        lv = _levels_array(levels, n)
+        k = _pairs_array(max_pairs, n)
+        self._check(self._L.wc_thin_budget(self._h, ctypes.c_void_p(d_payload), ctypes.c_void_p(d_offsets), units, n,
+                                           lv.ctypes.data, k.ctypes.data, ctypes.c_void_p(d_out), int(capacity),
+                                           ctypes.c_void_p(d_out_offsets), ctypes.c_void_p(d_kept),
+                                           ctypes.c_void_p(d_thresh or 0), ctypes.c_void_p(d_key or 0)))
+
+    def thin_thresh(self, d_payload: int, d_offsets: int, units, n: int, levels, thresh, d_out: int, capacity: int,
+                    d_out_offsets: int, d_kept: int):
+        """wc_thin_thresh: standard payloads -> what |c| > thresh[u][lvl - 1] keeps of them
+        (thresh: n x WC_MAX_LEVELS host floats).  wc_forward's slot layout."""
+        lv = _levels_array(levels, n)
+        t = _thin_thresh_array(thresh, n)
+        self._check(self._L.wc_thin_thresh(self._h, ctypes.c_void_p(d_payload), ctypes.c_void_p(d_offsets), units, n,
+                                           lv.ctypes.data, t.ctypes.data, ctypes.c_void_p(d_out), int(capacity),
+                                           ctypes.c_void_p(d_out_offsets), ctypes.c_void_p(d_kept)))
 
     def decompose_levels(self, d_cells: int, dtype: int, units, n: int, levels, d_flat: int):
         lv = _levels_array(levels, n)
@@ -618,6 +648,35 @@ class Context:
                                                           kept.ctypes.data, thresh.ctypes.data, key.ctypes.data,
                                                           rmse.ctypes.data if want_rmse else None))
         return payload, offsets, kept[:n], thresh[:n], key[:n], rmse[:n] if want_rmse else None
+
+    def thin_host(self, payload: np.ndarray, offsets: np.ndarray, units, n: int, levels=None, max_pairs=None,
+                  thresh=None):
+        """wc_thin_budget_host (max_pairs) or wc_thin_thresh_host (thresh: n x
+        WC_MAX_LEVELS) -> (out, out_offsets, kept, thresh [n, WC_MAX_LEVELS] or None, key or
+        None), packed as forward_host.  levels None: from the headers."""
+        if (max_pairs is None) == (thresh is None):
+            raise ValueError("exactly one of max_pairs and thresh")
+        p = np.ascontiguousarray(payload, np.uint8)
+        off = np.ascontiguousarray(offsets, np.uint64)
+        lv = None if levels is None else _levels_array(levels, n)
+        k = None if max_pairs is None else _pairs_array(max_pairs, n)
+        cap = thin_bound(units, n, k)
+        out = np.empty(cap, np.uint8)
+        out_offsets = np.zeros(n + 1, np.uint64)
+        kept = np.zeros(max(n, 1), np.uint32)
+        if k is not None:
+            th = np.zeros((max(n, 1), WC_MAX_LEVELS), np.float32)
+            key = np.zeros(max(n, 1), np.uint32)
+            self._check(self._L.wc_thin_budget_host(self._h, p.ctypes.data, off.ctypes.data, units, n,
+                                                    None if lv is None else lv.ctypes.data, k.ctypes.data,
+                                                    out.ctypes.data, cap, out_offsets.ctypes.data, kept.ctypes.data,
+                                                    th.ctypes.data, key.ctypes.data))
+            return out, out_offsets, kept[:n], th[:n], key[:n]
+        t = _thin_thresh_array(thresh, n)
+        self._check(self._L.wc_thin_thresh_host(self._h, p.ctypes.data, off.ctypes.data, units, n,
+                                                None if lv is None else lv.ctypes.data, t.ctypes.data,
+                                                out.ctypes.data, cap, out_offsets.ctypes.data, kept.ctypes.data))
+        return out, out_offsets, kept[:n], None, None
 
     def forward_levels_host(self, cells: np.ndarray, units, n: int, levels, keep: float,
                             thresh: float | None = None):
@@ -1010,6 +1069,40 @@ def tol_levels_threshold(counts: np.ndarray, levels: int, ncoeff: int, tol: floa
     if rc:
         raise WaveletError(rc, "wc_tol_levels_threshold: invalid argument")
     return [float(t[l]) for l in range(L)], float(b.value)
+
+
+def _thin_thresh_array(thresh, n):
+    """Per-unit, per-level thresholds as n x WC_MAX_LEVELS contiguous float32 (one value: the same everywhere)."""
+    t = np.asarray(thresh, np.float32)
+    if t.ndim == 0:
+        t = np.full((max(n, 1), WC_MAX_LEVELS), t, np.float32)
+    if t.shape != (max(n, 1), WC_MAX_LEVELS) and t.shape != (n, WC_MAX_LEVELS):
+        raise ValueError("thresh must be n x WC_MAX_LEVELS floats")
+    return np.ascontiguousarray(t, np.float32)
+
+
+def thin_bound(units, n: int, max_pairs=None) -> int:
+    """wc_thin_bound: the output extent of thin_budget (max_pairs) / thin_thresh (None)."""
+    k = None if max_pairs is None else _pairs_array(max_pairs, n)
+    return int(load_library().wc_thin_bound(units, n, None if k is None else k.ctypes.data))
+
+
+def thin_unit(payload, max_pairs=None, thresh=None):
+    """wc_thin_unit (host only): the rule on one standard payload -> (bytes, T, fp32
+    thresholds of levels 1..L).  Exactly one of max_pairs (K) and thresh (L floats)."""
+    p = np.frombuffer(bytes(payload), np.uint8)
+    out = np.empty(max(p.size, 20), np.uint8)
+    written = ctypes.c_size_t(0)
+    key = ctypes.c_uint32(0)
+    tout = np.zeros(WC_MAX_LEVELS, np.float32)
+    k = None if max_pairs is None else ctypes.c_uint32(int(max_pairs))
+    t = None if thresh is None else np.ascontiguousarray(np.resize(np.asarray(thresh, np.float32), WC_MAX_LEVELS))
+    rc = load_library().wc_thin_unit(p.ctypes.data, p.size, None if k is None else ctypes.addressof(k),
+                                     None if t is None else t.ctypes.data, out.ctypes.data, out.size,
+                                     ctypes.byref(written), ctypes.byref(key), tout.ctypes.data)
+    if rc != 0:
+        raise WaveletError(rc, "wc_thin_unit: refused")
+    return out[:written.value].tobytes(), int(key.value), tout[:payload_levels(bytes(payload[:20]))].copy()
 
 
 def budget_thresholds(key: int, levels: int):

@@ -175,6 +175,54 @@ def _standard_payloads(payloads: Sequence[bytes], device: int = 0) -> List[bytes
     return out
 
 
+def thin_payloads(payloads: Sequence[bytes], max_bytes=None, ratio=None, thresh=None, device: int = 0) -> List[bytes]:
+    """Payloads -> smaller payloads in the compressed domain (not in the reference;
+    wc_thin_budget_host / wc_thin_thresh_host): no cell and no dense coefficient
+    exists in between, and the result is what the forward's selection gives on the
+    array the payload decodes to.  max_bytes (an int or one per payload) and ratio
+    map to a pair budget exactly as in compress_payloads: each result keeps its
+    (max_bytes - 20) // 8 largest weighted coefficients and never more (ties at the
+    boundary are all dropped); ratio: max_bytes = max(20, floor(4 * N / ratio)) for
+    a box of N cells.  thresh (one float >= 0, or L per payload): keeps |c| > thresh
+    on every level (or thresh[i][lvl - 1]).  Exactly one of the three.  The levels
+    come from the headers.  Packed units are unpacked first; the results are
+    standard payloads."""
+    if sum(v is not None for v in (max_bytes, ratio, thresh)) != 1:
+        raise ValueError("exactly one of max_bytes, ratio and thresh")
+    if not payloads:
+        return []
+    std = _standard_payloads(payloads, device)
+    dims = _header_dims(std)
+    units, n, _ = capi.make_units(dims)
+    buf, offsets = _laid_out(std)
+    pairs = th = None
+    if thresh is not None:
+        th = np.zeros((n, capi.WC_MAX_LEVELS), np.float32)
+        if np.ndim(thresh) == 0:
+            th[:] = np.float32(thresh)
+        else:
+            if len(thresh) != n:
+                raise ValueError(f"thresh: one value or {n} rows")
+            for i, row in enumerate(thresh):
+                row = np.atleast_1d(np.asarray(row, np.float32))
+                th[i, :min(row.size, capi.WC_MAX_LEVELS)] = row[:capi.WC_MAX_LEVELS]
+                th[i, row.size:] = row[-1]
+    else:
+        if ratio is not None:
+            if not float(ratio) > 0:
+                raise ValueError(f"ratio: a positive number, not {ratio!r}")
+            budget = [max(20, int(4 * W * H * D / float(ratio))) for W, H, D in dims]
+        else:
+            budget = [int(max_bytes)] * n if np.ndim(max_bytes) == 0 else [int(v) for v in max_bytes]
+            if len(budget) != n:
+                raise ValueError(f"max_bytes: one value or {n} values")
+            if any(v < 20 for v in budget):
+                raise ValueError("max_bytes: a payload's header alone takes 20 bytes")
+        pairs = [min((v - 20) // 8, 0xFFFFFFFF) for v in budget]
+    out, off, kept = context(device).thin_host(buf, offsets, units, n, None, max_pairs=pairs, thresh=th)[:3]
+    return [capi.unit_payload(out, off, kept, i) for i in range(n)]
+
+
 def compress_payloads(boxes: Sequence[np.ndarray], keep: float, device: int = 0, levels: int = 1, rmse=None,
                       max_bytes=None, ratio=None, pack=None):
     """Batched forward path: list of Box3D -> list of serialized payload bytes.

@@ -486,7 +486,7 @@ void wc_ctx_destroy(wc_ctx* c) {
                       &c->plan.d_rdtiles, &c->rowinfo,    &c->istate,        &c->npairs,
                       &c->tol_in,        &c->tol_bins,       &c->h_thresh,       &c->h_bound,
                       &c->lv_side,       &c->pk_desc,        &c->pk_in,          &c->pk_out,
-                      &c->pk_off,        &c->pk_bytes};
+                      &c->pk_off,        &c->pk_bytes,       &c->thin};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (Plan& P : c->plan_cache) free_plan(P);
@@ -1399,6 +1399,178 @@ int wc_inverse_region(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_off
                       const int32_t* levels, const int32_t* reduce, const wc_region* regions, const wc_unit* out_units,
                       float* d_out) {
     return inverse_region(c, d_payload, d_offsets, units, n, levels, reduce, regions, out_units, d_out, nullptr);
+}
+
+}  // extern "C"
+
+namespace wc {
+
+// Thinning in the compressed domain (wc_thin.hip).  The plan of the units (dense,
+// without cell offsets: the one wc_inverse_region's decode uses) gives the pair
+// tiles and their look-back granules; the call's descriptors and split layout go
+// through the pinned block.  Everything of wc_ctx::thin is sized and grown here,
+// before the first launch; the state words are cleared on the stream.
+int thin_device(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                const int32_t* levels, const uint32_t* max_pairs, const float* thresh, bool full_slots, uint8_t* d_out,
+                uint64_t out_capacity, uint64_t* d_out_offsets, uint32_t* d_kept, float* d_thresh, uint32_t* d_key) {
+    const bool budget = max_pairs != nullptr;
+    int rc;
+    if ((rc = validate_levels(c, units, n, levels))) return rc;
+    std::vector<ThinDesc> desc(n);
+    uint64_t cursor = 4;
+    for (int u = 0; u < n; ++u) {
+        const wc_unit& f = units[u];
+        const uint64_t N = (uint64_t)f.nx * f.ny * f.nz;
+        const int L = levels[u];
+        ThinDesc& d = desc[u];
+        d = ThinDesc{};
+        d.dmagic = N ? rows_magic(f.nz) : 0;
+        d.hmagic = N ? rows_magic(f.ny) : 0;
+        d.W = f.nx;
+        d.H = f.ny;
+        d.D = f.nz;
+        d.want = L >= 2 ? -L : (int32_t)N;
+        d.N = (uint32_t)N;
+        d.L = (uint32_t)L;
+        d.slot = kLtSolo;
+        d.K = budget ? max_pairs[u] : 0u;
+        d.cap = budget && !full_slots ? (uint32_t)std::min<uint64_t>(d.K, N) : (uint32_t)N;
+        for (int l = 0; l < L && !budget; ++l) {
+            d.th[l] = thresh[(size_t)u * WC_MAX_LEVELS + l];
+            if (!(d.th[l] >= 0.0f))
+                return fail(c, WC_ERR_INVALID,
+                            "unit " + std::to_string(u) + ": threshold of level " + std::to_string(l + 1) +
+                                " is NaN or negative");
+        }
+        d.out_off = cursor;
+        cursor += 24 + 8ull * d.cap;
+    }
+    if (out_capacity < cursor) return fail(c, WC_ERR_INVALID, "out_capacity < wc_thin_bound");
+    {  // the input's length is not known here: what can be seen is its start inside the output's extent
+        const uintptr_t a0 = (uintptr_t)d_payload, a1 = a0 + 24, b0 = (uintptr_t)d_out, b1 = b0 + cursor;
+        if (a0 < b1 && b0 < a1) return fail(c, WC_ERR_INVALID, "out overlaps the payload buffer");
+    }
+    if ((rc = check_aligned(c, d_payload, "payload")) || (rc = check_aligned(c, d_offsets, "offsets", 8)) ||
+        (rc = check_aligned(c, d_out, "out")) || (rc = check_aligned(c, d_out_offsets, "out_offsets", 8)) ||
+        (rc = check_aligned(c, d_kept, "kept", 4)) || (rc = check_aligned(c, d_thresh, "thresh", 4)) ||
+        (rc = check_aligned(c, d_key, "key", 4)))
+        return rc;
+    if ((rc = set_device(c))) return rc;
+    std::vector<wc_unit> full(units, units + n);
+    for (wc_unit& u : full) u.cell_offset = 0;
+    const bool rows = c->opt_inv_rows;
+    c->opt_inv_rows = false;  // a dense plan: every unit's pair tiles in dtiles
+    rc = get_plan(c, full.data(), n);
+    c->opt_inv_rows = rows;
+    if (rc) return rc;
+    const Plan& P = c->plan;
+    // as build_leveltol: a unit of more than opt_tol_solo tiles is split into runs of `chunk` tiles
+    const uint32_t solo = (uint32_t)c->opt_tol_solo, chunk = std::min<uint32_t>(solo, 8);
+    std::vector<uint32_t> split;
+    std::vector<uint2> items;
+    uint64_t tiles = 0;
+    for (int u = 0; u < n; ++u) {
+        const UnitDev& d = P.units[u];
+        desc[u].dt_begin = d.dt_begin;
+        tiles += d.ndt;
+        if (!budget || d.ndt <= solo) continue;
+        desc[u].slot = (uint32_t)split.size();
+        split.push_back((uint32_t)u);
+        for (uint32_t t = 0; t < d.ndt; t += chunk) items.push_back(make_uint2((uint32_t)u, t));
+    }
+    const size_t nsplit = split.size(), nitems = items.size();
+    // the pinned blob: ThinDesc[n] | items[nitems] | split_units[nsplit]
+    const size_t o_items = sizeof(ThinDesc) * n, o_split = o_items + sizeof(uint2) * nitems,
+                 in_bytes = o_split + 4 * nsplit;
+    // wc_ctx::thin: [ticket[2][n] | keptw[n] | keyw[n] | status[2][tiles]] (cleared) | state[nsplit] | thresh[n][4] |
+    //               gbins[nsplit][4352] | s2[tiles * kFlatTile] | s1[tiles * kFlatTile]
+    const size_t o_status = round_up(16ull * n, 8), clear_bytes = o_status + 16ull * tiles,
+                 o_state = round_up(clear_bytes, 16), o_th = o_state + sizeof(BudgetState) * nsplit,
+                 o_bins = o_th + sizeof(float) * WC_MAX_LEVELS * n, o_s2 = o_bins + 4ull * 4352 * nsplit,
+                 o_s1 = round_up(o_s2 + 4ull * kFlatTile * tiles, 16), total = o_s1 + 8ull * kFlatTile * tiles;
+    uint8_t* pin = nullptr;
+    if ((rc = ensure(c, c->thin, total)) || (rc = pin_begin(c, in_bytes, in_bytes, &pin))) return rc;
+    std::memcpy(pin, desc.data(), sizeof(ThinDesc) * n);
+    if (nitems) std::memcpy(pin + o_items, items.data(), sizeof(uint2) * nitems);
+    if (nsplit) std::memcpy(pin + o_split, split.data(), 4 * nsplit);
+    if ((rc = pin_upload(c, in_bytes))) return rc;
+    uint8_t* s = (uint8_t*)c->thin.p;
+    const uint8_t* blob = (const uint8_t*)c->tol_in.p;
+    hipError_t e = hipMemsetAsync(s, 0, clear_bytes, c->stream);
+    if (e != hipSuccess) return hip_fail(c, e, "memset");
+    ThinLaunch a{};
+    a.desc = (const ThinDesc*)blob;
+    a.n = n;
+    a.tiles = (const FTile*)P.d_dtiles.p;
+    a.ntiles = (uint32_t)P.dtiles.size();
+    a.payload = d_payload;
+    a.offsets = d_offsets;
+    a.budget = budget;
+    a.ordered = use_ordered(c) ? (c->opt_reverse ? 2 : 1) : 0;
+    a.ticket[0] = (uint32_t*)s;
+    a.ticket[1] = (uint32_t*)s + n;
+    a.keptw = (uint32_t*)s + 2 * (size_t)n;
+    a.keyw = (uint32_t*)s + 3 * (size_t)n;
+    a.status[0] = (unsigned long long*)(s + o_status);
+    a.status[1] = a.status[0] + tiles;
+    a.state = (BudgetState*)(s + o_state);
+    a.thresh = d_thresh ? d_thresh : (float*)(s + o_th);
+    a.key_out = d_key;
+    a.gbins = (uint32_t*)(s + o_bins);
+    a.s2 = (uint32_t*)(s + o_s2);
+    a.s1 = (uint2*)(s + o_s1);
+    a.items = (const uint2*)(blob + o_items);
+    a.nitems = (uint32_t)nitems;
+    a.chunk = chunk;
+    a.split_units = (const uint32_t*)(blob + o_split);
+    a.nsplit = (uint32_t)nsplit;
+    a.out = d_out;
+    a.out_offsets = d_out_offsets;
+    a.kept = d_kept;
+    a.err = (uint32_t*)c->errflag.p;
+    StageTimer t(c, WC_STAGE_TOL);
+    if ((e = launch_thin(c->stream, a)) != hipSuccess) return hip_fail(c, e, "thin launch");
+    c->err_check_pending = true;  // malformed payloads surface at the next wc_synchronize
+    return WC_OK;
+}
+
+}  // namespace wc
+
+extern "C" {
+
+uint64_t wc_thin_bound(const wc_unit* units, int n, const uint32_t* max_pairs) {
+    uint64_t b = 4;
+    for (int i = 0; i < n; ++i) {
+        const uint64_t N = (uint64_t)units[i].nx * units[i].ny * units[i].nz;
+        b += 24 + 8 * (max_pairs ? std::min<uint64_t>(max_pairs[i], N) : N);
+    }
+    return b;
+}
+
+int wc_thin_budget(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                   const int32_t* levels, const uint32_t* max_pairs, uint8_t* d_out, uint64_t out_capacity,
+                   uint64_t* d_out_offsets, uint32_t* d_kept, float* d_thresh, uint32_t* d_key) {
+    if (!c) return WC_ERR_INVALID;
+    int rc;
+    if ((rc = validate_units(c, units, n))) return rc;
+    if (n == 0) return WC_OK;
+    if (!d_payload || !d_offsets || !levels || !max_pairs || !d_out || !d_out_offsets || !d_kept)
+        return fail(c, WC_ERR_INVALID, "null buffer");
+    return thin_device(c, d_payload, d_offsets, units, n, levels, max_pairs, nullptr, false, d_out, out_capacity,
+                       d_out_offsets, d_kept, d_thresh, d_key);
+}
+
+int wc_thin_thresh(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                   const int32_t* levels, const float* thresh, uint8_t* d_out, uint64_t out_capacity,
+                   uint64_t* d_out_offsets, uint32_t* d_kept) {
+    if (!c) return WC_ERR_INVALID;
+    int rc;
+    if ((rc = validate_units(c, units, n))) return rc;
+    if (n == 0) return WC_OK;
+    if (!d_payload || !d_offsets || !levels || !thresh || !d_out || !d_out_offsets || !d_kept)
+        return fail(c, WC_ERR_INVALID, "null buffer");
+    return thin_device(c, d_payload, d_offsets, units, n, levels, nullptr, thresh, false, d_out, out_capacity,
+                       d_out_offsets, d_kept, nullptr, nullptr);
 }
 
 // The decoders over packed units (wc_packsrc.h): wc_unpack followed by

@@ -31,6 +31,9 @@
 //                    (plain C++, linked alone with wc_packfmt.h by
 //                    tests/cpp/test_pack.cpp), and wc_pack, wc_unpack and their
 //                    _host forms
+//   wc_thinrule.cpp / wc_thinhost.cpp  thinning in the compressed domain: the rule on
+//                    one payload (wc_thin_unit, plain C++), wc_thin_bound and the
+//                    _host drivers of wc_thin_budget / wc_thin_thresh
 //   wc_coarsehost.cpp host side of the reduced-resolution inverse: wc_coarse_units,
 //                    the argument checks and wc_inverse_coarse_host (a call of
 //                    wc_regionhost.cpp's driver)
@@ -131,6 +134,9 @@ hipError_t launch_pack_units(hipStream_t, const PackDesc*, const FTile* tiles, u
 hipError_t launch_unpack_units(hipStream_t, const PackDesc*, const FTile* tiles, uint32_t ntiles, const uint8_t* packed,
                                const uint64_t* packed_offsets, uint64_t cap, int n, uint8_t* payload, uint64_t* offsets,
                                uint32_t* kept, uint32_t* err);
+
+// wc_thin.hip: the passes of wc_thin_budget / wc_thin_thresh (wc_internal.h ThinLaunch)
+hipError_t launch_thin(hipStream_t, const ThinLaunch&);
 
 struct DevBuf {
     void* p = nullptr;
@@ -260,6 +266,8 @@ struct wc_ctx {
     int pk_vbytes = 0;
     uint32_t pk_ntiles = 0;
     wc::DevBuf pk_in, pk_out, pk_off, pk_bytes;
+    // wc_thin_budget / wc_thin_thresh: per-call state, select bins and the two pair scratches (wc_thin.hip)
+    wc::DevBuf thin;
     std::unique_ptr<wc::HostPool> hpool;
     // uploads from pageable host memory: copied by upool's threads into pinned
     // bounce slots, each slot's copy to the device ordered by an event
@@ -333,6 +341,12 @@ int inverse_compact_host(wc_ctx* c, const uint8_t* payload, const uint64_t* offs
 
 // wc_packhost.cpp: no unit above WC_PACK_MAX_CELLS (the device calls over packed units)
 int validate_pack(wc_ctx* c, const wc_unit* units, int n);
+
+// wc_capi.cpp: wc_thin_budget (max_pairs) and wc_thin_thresh (thresh) after their null checks.
+// full_slots: the budget form with wc_forward's slot layout (cap_u = N_u), for launch_pack.
+int thin_device(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                const int32_t* levels, const uint32_t* max_pairs, const float* thresh, bool full_slots, uint8_t* d_out,
+                uint64_t out_capacity, uint64_t* d_out_offsets, uint32_t* d_kept, float* d_thresh, uint32_t* d_key);
 
 // Bracket one launch with events when profiling is on.
 struct StageTimer {

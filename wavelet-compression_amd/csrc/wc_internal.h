@@ -131,6 +131,54 @@ struct BudgetState {
 };
 static_assert(sizeof(BudgetState) == 16, "one 16-B load");
 
+// One unit of the compressed-domain thinning (wc_thin.hip).  Built per call: the
+// levels, the budget or thresholds and the output slot are not part of a plan.
+struct ThinDesc {
+    uint64_t dmagic;     // div_rows magic of D: row = floor(position / D)
+    uint64_t hmagic;     // div_rows magic of H: I = floor(row / H)
+    uint64_t out_off;    // the unit's output slot: prefix of 24 + 8 * cap, == 4 (mod 8)
+    int32_t W, H, D;     // the box
+    int32_t want;        // the header's ncoeff field: W*H*D, or -L for L >= 2
+    uint32_t N;          // W*H*D
+    uint32_t L;
+    uint32_t dt_begin;   // the unit's first pair tile: look-back granules and scratch rows
+    uint32_t slot;       // kLtSolo, or the unit's index among the split units (its global bins)
+    uint32_t K;          // budget form: max_pairs
+    uint32_t cap;        // pairs the slot holds: min(K, N), or N
+    float th[4];         // threshold form: t_1..t_L
+};
+static_assert(sizeof(ThinDesc) == 80, "descriptor of 8-B members first");
+
+// What launch_thin (wc_thin.hip) takes: the passes of wc_thin_budget / wc_thin_thresh over the plan's
+// decode tiles of the units (budget: the radix select between the scan and the compaction).
+struct ThinLaunch {
+    const ThinDesc* desc;
+    int n;
+    const FTile* tiles;
+    uint32_t ntiles;
+    const uint8_t* payload;
+    const uint64_t* offsets;
+    bool budget;
+    int ordered;
+    uint32_t* ticket[2];            // scan, compaction: per unit, zeroed
+    unsigned long long* status[2];  // their look-back granules, per decode tile, zeroed
+    uint2* s1;                      // {key, pos} per pair
+    uint32_t* s2;                   // positions of the kept pairs
+    uint32_t* keyw;                 // per unit: T (zeroed: the threshold form's)
+    uint32_t* keptw;                // per unit: kept pairs (zeroed)
+    float* thresh;                  // n x WC_MAX_LEVELS (budget)
+    uint32_t* key_out;              // the caller's d_key or null
+    const uint2* items;             // split units' tile runs of `chunk` tiles
+    uint32_t nitems, chunk;
+    const uint32_t* split_units;
+    uint32_t nsplit;
+    uint32_t* gbins;                // nsplit x 4352 words
+    BudgetState* state;             // nsplit
+    uint8_t* out;
+    uint64_t* out_offsets;
+    uint32_t* kept;
+    uint32_t* err;
+};
 // One unit of the packed-payload transcoders (wc_pack.hip): the box, the unit's
 // slot in the packed buffer (wc_packed_bound's scheme) and its slot in the
 // standard payload buffer (wc_payload_bound's).  Kept on the device while a
