@@ -45,6 +45,7 @@ struct FakeStream {
     std::condition_variable cv, idle;
     std::deque<std::function<void()>> q;
     bool stop = false, busy = false;
+    std::atomic<long> copies{0};  // hipMemcpyAsync calls enqueued since the last hipStreamSynchronize that returned success
     std::thread th;
     FakeStream() : th([this] { loop(); }) {}
     ~FakeStream() {
@@ -94,6 +95,7 @@ std::map<uintptr_t, Alloc> g_allocs;      // live hipMalloc / hipHostMalloc rang
 std::vector<FakeStream*> g_streams;       // live streams (hipFree drains them all)
 thread_local hipError_t t_last = hipSuccess;
 std::map<std::string, int> g_fail;        // api -> calls left until the injected failure
+std::map<std::string, long> g_count;      // api -> calls that could have been made to fail, so far
 std::atomic<long> g_calls{0};
 
 FakeStream* default_stream() {
@@ -111,6 +113,7 @@ FakeStream* S(hipStream_t s) { return s ? s : default_stream(); }
 bool injected(const char* api) {
     ++g_calls;
     std::lock_guard<std::mutex> lk(g_mu);
+    ++g_count[api];
     auto it = g_fail.find(api);
     if (it == g_fail.end()) return false;
     if (--it->second > 0) return false;
@@ -190,9 +193,19 @@ void clear_failures() {
     g_fail.clear();
 }
 long calls() { return g_calls.load(); }
+long count(const char* api) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    return g_count[api];
+}
 size_t live_allocations() {
     std::lock_guard<std::mutex> lk(g_mu);
     return g_allocs.size();
+}
+long pending_copies() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    long k = 0;
+    for (FakeStream* s : g_streams) k += s->copies.load();
+    return k;
 }
 }  // namespace fake
 
@@ -214,7 +227,13 @@ hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKin
     if (injected(api) || injected("hipMemcpyAsync")) return ret(hipErrorUnknown);
     const bool pageable = (kind == hipMemcpyHostToDevice && type_of(src) == hipMemoryTypeUnregistered) ||
                           (kind == hipMemcpyDeviceToHost && type_of(dst) == hipMemoryTypeUnregistered);
+    ++S(s)->copies;
     enqueue(s, [=] { std::memcpy(dst, src, bytes); }, pageable);
+    return hipSuccess;
+}
+hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind) {
+    if (injected("hipMemcpy")) return ret(hipErrorUnknown);
+    enqueue(nullptr, [=] { std::memcpy(dst, src, bytes); }, true);
     return hipSuccess;
 }
 hipError_t hipMemsetAsync(void* dst, int v, size_t bytes, hipStream_t s) {
@@ -247,6 +266,7 @@ hipError_t hipStreamDestroy(hipStream_t s) {
 hipError_t hipStreamSynchronize(hipStream_t s) {
     if (injected("hipStreamSynchronize")) return ret(hipErrorUnknown);
     S(s)->drain();
+    S(s)->copies = 0;
     return hipSuccess;
 }
 hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {

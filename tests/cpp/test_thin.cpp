@@ -1,7 +1,7 @@
 // test_thin.cpp — the host side of the compressed-domain thinning on the CPU, for the
 // ASan + UBSan build (`make thinsan`, run by tests/test_thin_san.py): wc_thin_unit
 // (wc_thinrule.cpp) and the host drivers wc_thin_budget_host / wc_thin_thresh_host
-// (wc_thinhost.cpp) over the fake HIP runtime of tests/cpp/fake_device.cpp.  No GPU
+// (wc_thinhost.cpp, on wc_hostserial.cpp's driver) over the fake HIP runtime of tests/cpp/fake_device.cpp.  No GPU
 // and no kernel: the device entry point the drivers call (wc::thin_device) is
 // restated here on wc_thin_unit, into wc_forward's slot layout, as the real one
 // writes it.  Every buffer the rule or a driver reads or writes is a heap block of
@@ -46,15 +46,6 @@ static int g_checks = 0, g_fail = 0;
             }                                                                     \
         }                                                                         \
     } while (0)
-
-// the two device entry points wc_levelshost.cpp links; nothing here calls its _host forms
-extern "C" int wc_forward_levels(wc_ctx*, const void*, int, const wc_unit*, int, const int32_t*, double, const float*,
-                                 uint8_t*, uint64_t, uint64_t*, uint32_t*) {
-    std::abort();
-}
-extern "C" int wc_inverse_levels(wc_ctx*, const uint8_t*, const uint64_t*, const wc_unit*, int, const int32_t*, float*) {
-    std::abort();
-}
 
 extern "C" uint64_t wc_thin_bound(const wc_unit* units, int n, const uint32_t* max_pairs) {  // wc_capi.cpp's
     uint64_t b = 4;

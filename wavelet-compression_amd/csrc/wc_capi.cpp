@@ -5,16 +5,20 @@
 // cached batch plans (wc_plan.cpp), and turns a batch of units into kernel
 // launches.  No CPU fallback exists: every computing entry point launches HIP
 // kernels and fails with WC_ERR_HIP if the device or code object is absent.
-// The _host entry points are in wc_hostpipe.cpp (wc_forward_tol_host and the
-// host-only wc_tol_threshold: wc_tolhost.cpp; wc_forward_levels_tol_host:
+// The _host entry points are in wc_hostpipe.cpp; those of the opt-in modes are
+// calls of the two serial drivers of wc_hostserial.cpp (wc_forward_tol_host and
+// the host-only wc_tol_threshold: wc_tolhost.cpp; wc_forward_levels_tol_host:
 // wc_leveltolhost.cpp; the host-only wc_tol_levels_threshold: wc_leveltolrule.cpp;
 // wc_forward_levels_budget_host: wc_budgethost.cpp; the host-only wc_budget_select
 // and wc_budget_thresholds: wc_budgetrule.cpp; wc_pack, wc_unpack and their _host
 // forms: wc_packhost.cpp; the packed format's host-only rule: wc_packrule.cpp;
-// wc_forward_levels_host and wc_inverse_levels_host: wc_levelshost.cpp;
+// the packed decoders' _host forms: wc_packdecodehost.cpp;
+// wc_forward_levels_host and wc_inverse_levels_host: wc_levelshost.cpp; the
+// host-only wc_levels_for and wc_payload_levels: wc_levelsrule.cpp;
 // wc_inverse_coarse_host and wc_coarse_units: wc_coarsehost.cpp;
-// wc_inverse_region_host and the driver it shares with wc_inverse_coarse_host:
-// wc_regionhost.cpp; wc_region_align and wc_region_units: wc_regionrule.cpp).
+// wc_inverse_region_host and the checks it shares with wc_inverse_coarse_host:
+// wc_regionhost.cpp; wc_region_align and wc_region_units: wc_regionrule.cpp;
+// wc_thin_budget_host and wc_thin_thresh_host: wc_thinhost.cpp).
 //
 // Forward path per batch (wc_forward), every unit shape: K1 k_transform{,_fast}
 // -> flat coefficients in HBM scratch (sparse staging: only the flagged

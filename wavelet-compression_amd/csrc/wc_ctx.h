@@ -13,12 +13,17 @@
 //                    own: it calls the device entry points), also built
 //                    against a CPU fake of the HIP runtime for the sanitizer
 //                    tests (tests/cpp/test_hostpipe.cpp)
+//   wc_hostserial.cpp the two serial drivers of the opt-in modes' _host entry points
+//                    (unit runs one after another on the context's stream):
+//                    forward_serial (cells in) and payload_serial (payload bytes
+//                    in), the run splitter, the span helpers, the one error exit;
+//                    built against the CPU fake too (tests/cpp/test_hostserial.cpp)
 //   wc_tolhost.cpp   host side of the RMSE-tolerance mode: the selection rule
 //                    on one unit's counts, the mode's argument checks and
-//                    wc_forward_tol_host (unit runs one after another)
-//   wc_levelshost.cpp host side of the multi-level mode: wc_levels_for,
-//                    wc_payload_levels, the mode's argument checks and the
-//                    _levels_host entry points
+//                    wc_forward_tol_host (a call of forward_serial)
+//   wc_levelsrule.cpp / wc_levelshost.cpp  the multi-level mode: wc_levels_for,
+//                    wc_payload_levels and the argument checks (no device entry
+//                    point called), and the _levels_host entry points
 //   wc_leveltolrule.cpp / wc_leveltolhost.cpp  the RMSE tolerance on the
 //                    multi-level transform: the per-level selection rule (plain
 //                    C++, linked alone by tests/cpp/test_leveltol.cpp) and
@@ -33,15 +38,16 @@
 //                    _host forms
 //   wc_thinrule.cpp / wc_thinhost.cpp  thinning in the compressed domain: the rule on
 //                    one payload (wc_thin_unit, plain C++), wc_thin_bound and the
-//                    _host drivers of wc_thin_budget / wc_thin_thresh
+//                    _host forms of wc_thin_budget / wc_thin_thresh (payload_serial)
 //   wc_coarsehost.cpp host side of the reduced-resolution inverse: wc_coarse_units,
 //                    the argument checks and wc_inverse_coarse_host (a call of
-//                    wc_regionhost.cpp's driver)
+//                    wc_regionhost.cpp's inverse_compact_host)
 //   wc_regionrule.cpp / wc_regionhost.cpp  the sub-box inverse: wc_region_align
 //                    and wc_region_units (plain C++, linked alone with
 //                    wc_regionmap.h by tests/cpp/test_regionrule.cpp), the
-//                    argument checks, wc_inverse_region_host and the host driver
-//                    of both modes
+//                    argument checks, wc_inverse_region_host and what it shares
+//                    with wc_inverse_coarse_host (inverse_compact_host)
+//   wc_packdecodehost.cpp  the _host forms of the decoders over packed units
 #pragma once
 
 #include "wavelet_amd.h"
@@ -49,6 +55,7 @@
 #include "wc_internal.h"
 
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <memory>
 #include <string>
@@ -319,9 +326,50 @@ int host_threads_default();
 // wc_tolhost.cpp
 int validate_tol(wc_ctx* c, const wc_unit* units, int n, const double* tol);
 
-// wc_levelshost.cpp
+// wc_levelsrule.cpp
 int validate_levels(wc_ctx* c, const wc_unit* units, int n, const int32_t* levels);
-std::vector<int> level_runs(const wc_ctx* c, const wc_unit* units, int n);
+
+// wc_hostserial.cpp: the serial host drivers (the callers have checked their arguments and called set_device)
+// end[u] of a standard payload from its header; with from_headers, each unit's L as well
+int payload_ends(wc_ctx* c, const uint8_t* payload, const uint64_t* offsets, int n, std::vector<uint64_t>& end,
+                 std::vector<int32_t>* from_headers);
+// a per-unit result, back at the call's end: stride bytes per unit from dev to host (NULL: not asked for)
+struct UnitResult {
+    const void* dev;
+    void* host;
+    size_t stride;
+};
+// the device call of run [a, a + m) into wc_forward's slots, and the round trip of its payloads (rmse only)
+using ForwardStep = std::function<int(int a, int m, const void* d_cells, uint8_t* d_payload, uint64_t run_bound,
+                                      uint64_t* d_offsets, uint32_t* d_kept)>;
+using RoundTrip = std::function<int(int a, int m, const uint8_t* d_payload, const uint64_t* d_offsets)>;
+// wc_levelshost.cpp: the round trip of the level modes, wc_inverse_levels + wc_rmse
+RoundTrip levels_round_trip(wc_ctx* c, int dtype, const wc_unit* units, const int32_t* levels);
+// rmse: c->h_out (the round trip's cells) and c->h_rmse (double per unit, global index) are the driver's
+int forward_serial(wc_ctx* c, const void* cells, int dtype, const wc_unit* units, int n, uint8_t* payload, uint64_t cap,
+                   uint64_t* offsets, uint32_t* kept, double* rmse, const ForwardStep& step, const RoundTrip& trip,
+                   std::vector<UnitResult> results);
+// the device call of run [a, a + m) on the uploaded bytes (readable below bytes_cap) into c->h_out
+using PayloadStep =
+    std::function<int(int a, int m, const uint8_t* d_bytes, const uint64_t* d_offsets, uint64_t bytes_cap)>;
+struct SerialOut {
+    uint64_t shift = 0, slack = 16;  // a run's bytes upload at shift + (their start & 7); c->h_payload has slack bytes more
+    // either the boxes of out_units back from c->h_out (of out_bytes); checked: synchronize and
+    // check_kernel_errors after each run's device call, before that run's cells cross back
+    const wc_unit* out_units = nullptr;
+    float* out = nullptr;
+    uint64_t out_bytes = 0;
+    bool checked = false;
+    // or (payload set) c->h_out holds the run's slots in wc_forward's layout: forward_serial's packed tail
+    uint8_t* payload = nullptr;
+    uint64_t cap = 0;
+    uint64_t* out_offsets = nullptr;
+    uint32_t* kept = nullptr;
+    std::vector<UnitResult> results;
+};
+// unit u's bytes are [offsets[u], end[u]); runs are split by the cells of units
+int payload_serial(wc_ctx* c, const uint8_t* bytes, const uint64_t* offsets, const uint64_t* end, const wc_unit* units,
+                   int n, const PayloadStep& step, const SerialOut& o);
 
 // wc_budgethost.cpp
 int validate_budget(wc_ctx* c, const wc_unit* units, int n, const int32_t* levels);
@@ -334,7 +382,7 @@ uint64_t rows_magic(int32_t d);
 // wc_regionhost.cpp (reduce NULL = all 0)
 int validate_region(wc_ctx* c, const wc_unit* units, int n, const int32_t* levels, const int32_t* reduce,
                     const wc_region* regions, const wc_unit* out_units);
-// the host driver of wc_inverse_coarse_host (regions NULL) and wc_inverse_region_host
+// wc_inverse_coarse_host (regions NULL) and wc_inverse_region_host after their null checks
 int inverse_compact_host(wc_ctx* c, const uint8_t* payload, const uint64_t* offsets, const wc_unit* units, int n,
                          const int32_t* levels, const int32_t* reduce, const wc_region* regions,
                          const wc_unit* out_units, float* out);

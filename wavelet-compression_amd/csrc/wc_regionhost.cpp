@@ -1,15 +1,14 @@
 // wc_regionhost.cpp — host side of the sub-box inverse (include/wavelet_amd.h
 // wc_inverse_region): the mode's argument checks, wc_inverse_region_host and
-// the driver it shares with wc_inverse_coarse_host.  (wc_region_align and
-// wc_region_units are in wc_regionrule.cpp, plain C++.)
+// inverse_compact_host, which it shares with wc_inverse_coarse_host.
+// (wc_region_align and wc_region_units are in wc_regionrule.cpp, plain C++.)
 //
-// The driver runs its unit runs (WC_OPT_HOST_CHUNK, by the cells of the
-// full-size units) one after another on the context's stream, as
-// wc_inverse_levels_host does; only the derived units' cells cross back.
+// inverse_compact_host is the two modes' checks and a call of payload_serial
+// (wc_hostserial.cpp): runs by the cells of the full-size units, only the
+// derived units' cells cross back.
 #include "wc_ctx.h"
 
 #include <algorithm>
-#include <cstring>
 #include <string>
 #include <vector>
 
@@ -65,27 +64,14 @@ int validate_region(wc_ctx* c, const wc_unit* units, int n, const int32_t* level
 
 // wc_inverse_coarse_host (regions NULL) and wc_inverse_region_host after their
 // null checks: the levels (from the headers where the caller passes none), the
-// mode's checks, then run by run the upload, the device call and the readback.
+// mode's checks, then payload_serial with the mode's device call.
 int inverse_compact_host(wc_ctx* c, const uint8_t* payload, const uint64_t* offsets, const wc_unit* units, int n,
                          const int32_t* levels, const int32_t* reduce, const wc_region* regions,
                          const wc_unit* out_units, float* out) {
     int rc;
-    // unit u's bytes: its header and the nrle pairs the header announces, as wc_inverse_levels_host
-    std::vector<uint64_t> end(n);
+    std::vector<uint64_t> end;
     std::vector<int32_t> from_headers;
-    if (!levels) from_headers.resize(n);
-    for (int i = 0; i < n; ++i) {
-        if (offsets[i] & 3) return fail(c, WC_ERR_INVALID, "offsets must be multiples of 4");
-        int32_t nrle;
-        std::memcpy(&nrle, payload + offsets[i] + 16, 4);
-        end[i] = offsets[i] + 20 + 8ull * (uint64_t)std::max(nrle, 0);
-        if (!levels) {  // each unit's L from its header
-            int L = 0;
-            if (wc_payload_levels(payload + offsets[i], 20, &L) != WC_OK)
-                return fail(c, WC_ERR_FORMAT, "unit " + std::to_string(i) + ": malformed payload header");
-            from_headers[i] = L;
-        }
-    }
+    if ((rc = payload_ends(c, payload, offsets, n, end, levels ? nullptr : &from_headers))) return rc;
     if (!levels) levels = from_headers.data();
     if ((rc = validate_levels(c, units, n, levels)) ||
         (rc = regions ? validate_region(c, units, n, levels, reduce, regions, out_units)
@@ -94,70 +80,20 @@ int inverse_compact_host(wc_ctx* c, const uint8_t* payload, const uint64_t* offs
     if (!regions && std::all_of(reduce, reduce + n, [](int32_t r) { return r == 0; }))
         return wc_inverse_levels_host(c, payload, offsets, out_units, n, levels, out);
     if ((rc = set_device(c))) return rc;
-    const uint64_t ext = cells_extent(out_units, n);
-    const std::vector<int> rb = level_runs(c, units, n);
-    const int nr = (int)rb.size() - 1;
-    // a run's payload bytes [lo, hi) upload to the same distance from an 8-B
-    // boundary (pairs stay 8-B aligned); its offsets are rebased to that copy
-    auto span = [&](int r, uint64_t& lo, uint64_t& hi) {
-        lo = UINT64_MAX;
-        hi = 0;
-        for (int i = rb[r]; i < rb[r + 1]; ++i) {
-            lo = std::min(lo, offsets[i]);
-            hi = std::max(hi, end[i]);
-        }
-    };
-    uint64_t run_bytes = 0;
-    int run_units = 0;
-    for (int r = 0; r < nr; ++r) {
-        uint64_t lo, hi;
-        span(r, lo, hi);
-        run_bytes = std::max(run_bytes, hi - lo);
-        run_units = std::max(run_units, rb[r + 1] - rb[r]);
-    }
-    if ((rc = ensure(c, c->h_payload, run_bytes + 16)) || (rc = ensure(c, c->h_out, sizeof(float) * ext + 16)) ||
-        (rc = ensure(c, c->h_offsets, sizeof(uint64_t) * run_units)))
-        return rc;
-    std::vector<uint64_t> ro(run_units);
-    for (int r = 0; r < nr; ++r) {
-        const int a = rb[r], m = rb[r + 1] - rb[r];
-        uint64_t p0, p1;
-        span(r, p0, p1);
-        const uint64_t shift = p0 & 7;
-        for (int i = 0; i < m; ++i) ro[i] = offsets[a + i] - p0 + shift;
-        hipError_t e;
-        if ((e = hipMemcpyAsync((uint8_t*)c->h_payload.p + shift, payload + p0, p1 - p0, hipMemcpyHostToDevice,
-                                c->stream)) != hipSuccess ||
-            (e = hipMemcpyAsync(c->h_offsets.p, ro.data(), sizeof(uint64_t) * m, hipMemcpyHostToDevice, c->stream)) !=
-                hipSuccess)
-            return hip_fail(c, e, "payload upload");
-        const uint8_t* d_payload = (const uint8_t*)c->h_payload.p;
-        const uint64_t* d_offsets = (const uint64_t*)c->h_offsets.p;
-        float* d_out = (float*)c->h_out.p;
-        rc = regions ? wc_inverse_region(c, d_payload, d_offsets, units + a, m, levels + a,
-                                         reduce ? reduce + a : nullptr, regions + a, out_units + a, d_out)
-                     : wc_inverse_coarse(c, d_payload, d_offsets, units + a, m, levels + a, reduce + a, out_units + a,
-                                         d_out);
-        if (rc) {
-            (void)hipStreamSynchronize(c->stream);
-            return rc;
-        }
-        // the units' boxes, back-to-back ones in one copy (cells no unit owns stay as they were)
-        e = hipSuccess;
-        for (int i = a; i < a + m && e == hipSuccess;) {
-            uint64_t lo = out_units[i].cell_offset,
-                     hi = lo + (uint64_t)out_units[i].nx * out_units[i].ny * out_units[i].nz;
-            for (++i; i < a + m && out_units[i].cell_offset == hi; ++i)
-                hi += (uint64_t)out_units[i].nx * out_units[i].ny * out_units[i].nz;
-            if (hi > lo)
-                e = hipMemcpyAsync(out + lo, (const float*)d_out + lo, sizeof(float) * (hi - lo),
-                                   hipMemcpyDeviceToHost, c->stream);
-        }
-        // ro is rewritten by the next run: the uploads have finished after this synchronize
-        const hipError_t es = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess || es != hipSuccess) return hip_fail(c, e != hipSuccess ? e : es, "box readback");
-    }
-    return check_kernel_errors(c);
+    SerialOut o;
+    o.out_units = out_units;
+    o.out = out;
+    o.out_bytes = sizeof(float) * cells_extent(out_units, n) + 16;
+    return payload_serial(
+        c, payload, offsets, end.data(), units, n,
+        [&](int a, int m, const uint8_t* d_payload, const uint64_t* d_offsets, uint64_t) {
+            float* d_out = (float*)c->h_out.p;
+            return regions ? wc_inverse_region(c, d_payload, d_offsets, units + a, m, levels + a,
+                                               reduce ? reduce + a : nullptr, regions + a, out_units + a, d_out)
+                           : wc_inverse_coarse(c, d_payload, d_offsets, units + a, m, levels + a, reduce + a,
+                                               out_units + a, d_out);
+        },
+        o);
 }
 
 }  // namespace wc

@@ -3,14 +3,13 @@
 // rule on one payload, wc_thin_unit, is in wc_thinrule.cpp, plain C++; the device
 // entry points are in wc_capi.cpp.)
 //
-// As wc_inverse_region_host, the unit runs (WC_OPT_HOST_CHUNK, by the cells of the
-// units) go one after another on the context's stream: upload the run's payload
-// bytes, the device call into wc_forward's slot layout, pack the slots densely
+// thin_host is the checks of both forms and a call of payload_serial
+// (wc_hostserial.cpp) with the packed-run tail: per run the payload bytes up, the
+// device call into wc_forward's slot layout, the slots packed densely
 // (wc_compact.hip, as wc_forward_host does), download.  Only payload bytes cross
 // the bus.  A unit whose header disagrees fails the call before anything runs.
 #include "wc_ctx.h"
 
-#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -50,86 +49,29 @@ int thin_host(wc_ctx* c, const uint8_t* payload, const uint64_t* offsets, const 
                     return fail(c, WC_ERR_INVALID, "unit " + std::to_string(i) + ": a threshold is NaN or negative");
     if (cap < wc_thin_bound(units, n, max_pairs)) return fail(c, WC_ERR_INVALID, "out_capacity < wc_thin_bound");
     if ((rc = set_device(c))) return rc;
-    const std::vector<int> rb = level_runs(c, units, n);
-    const int nr = (int)rb.size() - 1;
-    auto span = [&](int r, uint64_t& lo, uint64_t& hi) {
-        lo = UINT64_MAX;
-        hi = 0;
-        for (int i = rb[r]; i < rb[r + 1]; ++i) {
-            lo = std::min(lo, offsets[i]);
-            hi = std::max(hi, end[i]);
-        }
-    };
-    uint64_t run_bytes = 0, run_bound = 0;
-    int run_units = 0;
-    for (int r = 0; r < nr; ++r) {
-        uint64_t lo, hi;
-        span(r, lo, hi);
-        run_bytes = std::max(run_bytes, hi - lo);
-        run_bound = std::max(run_bound, wc_payload_bound(units + rb[r], rb[r + 1] - rb[r]));
-        run_units = std::max(run_units, rb[r + 1] - rb[r]);
-    }
-    if ((rc = ensure(c, c->h_payload, run_bytes + 32)) || (rc = ensure(c, c->h_out, run_bound)) ||
-        (rc = ensure(c, c->h_packed, run_bound)) || (rc = ensure(c, c->h_offsets, sizeof(uint64_t) * (run_units + 1))) ||
-        (rc = ensure(c, c->pk_off, sizeof(uint64_t) * (run_units + 1))) ||
-        (rc = ensure(c, c->h_poff, sizeof(uint64_t) * (run_units + 1))) || (rc = ensure(c, c->h_kept, 4ull * run_units)) ||
+    // thin_device's own outputs: the slot offsets of a run, the thresholds and keys of the budget form
+    if ((rc = ensure(c, c->pk_off, sizeof(uint64_t) * ((size_t)n + 1))) ||
         (rc = ensure(c, c->h_thresh, sizeof(float) * WC_MAX_LEVELS * n)) || (rc = ensure(c, c->h_bound, sizeof(uint32_t) * n)))
         return rc;
-    std::vector<uint64_t> ro(run_units), po(run_units + 1);
-    uint64_t R = 4;  // run r's packed bytes [4, end) land at R (== 4 mod 8)
-    for (int r = 0; r < nr; ++r) {
-        const int a = rb[r], m = rb[r + 1] - rb[r];
-        uint64_t p0, p1;
-        span(r, p0, p1);
-        const uint64_t shift = 16 + (p0 & 7);  // the copy keeps the bytes' distance from an 8-B boundary
-        for (int i = 0; i < m; ++i) ro[i] = offsets[a + i] - p0 + shift;
-        hipError_t e;
-        if ((e = hipMemcpyAsync((uint8_t*)c->h_payload.p + shift, payload + p0, p1 - p0, hipMemcpyHostToDevice,
-                                c->stream)) != hipSuccess ||
-            (e = hipMemcpyAsync(c->h_offsets.p, ro.data(), sizeof(uint64_t) * m, hipMemcpyHostToDevice, c->stream)) !=
-                hipSuccess)
-            return hip_fail(c, e, "payload upload");
-        uint32_t* dkept = (uint32_t*)c->h_kept.p;
-        uint64_t* dpoff = (uint64_t*)c->h_poff.p;
-        rc = thin_device(c, (const uint8_t*)c->h_payload.p, (const uint64_t*)c->h_offsets.p, units + a, m, lv.data() + a,
-                         max_pairs ? max_pairs + a : nullptr, thresh ? thresh + (size_t)WC_MAX_LEVELS * a : nullptr, true,
-                         (uint8_t*)c->h_out.p, run_bound, (uint64_t*)c->pk_off.p, dkept,
-                         max_pairs ? (float*)c->h_thresh.p + (size_t)WC_MAX_LEVELS * a : nullptr,
-                         max_pairs ? (uint32_t*)c->h_bound.p + a : nullptr);
-        if (rc == WC_OK) {
-            // the plan thin_device left is the run's units': its slots are wc_forward's
-            e = launch_pack(c->stream, (const UnitDev*)c->plan.d_units.p, m, dkept, (const uint8_t*)c->h_out.p, dpoff,
-                            (uint8_t*)c->h_packed.p);
-            if (e != hipSuccess) rc = hip_fail(c, e, "pack launch");
-        }
-        if (rc) {
-            (void)hipStreamSynchronize(c->stream);
-            return rc;
-        }
-        if ((e = hipMemcpyAsync(po.data(), dpoff, sizeof(uint64_t) * (m + 1), hipMemcpyDeviceToHost, c->stream)) !=
-                hipSuccess ||
-            (e = hipMemcpyAsync(kept + a, dkept, 4ull * m, hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
-            (e = hipStreamSynchronize(c->stream)) != hipSuccess)
-            return hip_fail(c, e, "sizes readback");
-        if (R - 4 + po[m] > cap) return fail(c, WC_ERR_INVALID, "out_capacity");
-        for (int i = 0; i < m; ++i) out_offsets[a + i] = R - 4 + po[i];
-        const uint64_t bytes = po[m] - 4;
-        if (bytes && (e = hipMemcpyAsync(out + R, (const uint8_t*)c->h_packed.p + 4, bytes, hipMemcpyDeviceToHost,
-                                         c->stream)) != hipSuccess)
-            return hip_fail(c, e, "payload readback");
-        // ro and the staging are rewritten by the next run
-        if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return hip_fail(c, e, "payload readback");
-        R += po[m];
-    }
-    out_offsets[n] = R - 4;
-    hipError_t e = hipSuccess;
-    if (max_pairs && thresh_out)
-        e = hipMemcpyAsync(thresh_out, c->h_thresh.p, sizeof(float) * WC_MAX_LEVELS * n, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && max_pairs && key)
-        e = hipMemcpyAsync(key, c->h_bound.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess || es != hipSuccess) return hip_fail(c, e != hipSuccess ? e : es, "results readback");
-    return check_kernel_errors(c);
+    SerialOut o;
+    o.shift = 16;
+    o.slack = 32;
+    o.payload = out;
+    o.cap = cap;
+    o.out_offsets = out_offsets;
+    o.kept = kept;
+    if (max_pairs)
+        o.results = {{c->h_thresh.p, thresh_out, sizeof(float) * WC_MAX_LEVELS}, {c->h_bound.p, key, sizeof(uint32_t)}};
+    return payload_serial(
+        c, payload, offsets, end.data(), units, n,
+        [&](int a, int m, const uint8_t* d_payload, const uint64_t* d_offsets, uint64_t) {
+            return thin_device(c, d_payload, d_offsets, units + a, m, lv.data() + a, max_pairs ? max_pairs + a : nullptr,
+                               thresh ? thresh + (size_t)WC_MAX_LEVELS * a : nullptr, true, (uint8_t*)c->h_out.p,
+                               wc_payload_bound(units + a, m), (uint64_t*)c->pk_off.p, (uint32_t*)c->h_kept.p,
+                               max_pairs ? (float*)c->h_thresh.p + (size_t)WC_MAX_LEVELS * a : nullptr,
+                               max_pairs ? (uint32_t*)c->h_bound.p + a : nullptr);
+        },
+        o);
 }
 
 }  // namespace
