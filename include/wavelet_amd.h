@@ -607,6 +607,108 @@ int wc_thin_thresh_host(wc_ctx* ctx, const uint8_t* payload, const uint64_t* off
                         const int32_t* levels, const float* thresh, uint8_t* out, uint64_t out_capacity,
                         uint64_t* out_offsets, uint32_t* kept);
 
+/* Opt-in progressive layers in the compressed domain (not in the reference): the
+ * complement of a thinning, and the union of payloads.  A payload becomes a stack
+ * of layers; any prefix of the stack, merged, is a standard payload every decoder
+ * reads unchanged.  No cell and no dense coefficient exists for either call.
+ *
+ * The rule.  P is a standard payload of a unit W x H x D with L levels, N = W*H*D.
+ * A(P) and the positions p_k are the thinning rule's above: exact 64-bit sums, a
+ * pair at or past N is dropped.
+ *   canon(P) = thin_thresh(P, 0, .., 0): the pairs of P below N whose magnitude
+ *     bits m satisfy 1 <= m <= 0x7F800000 (no +-0, no NaN), runs recomputed.  Every
+ *     payload an encoder of this project emits is its own canonical form.
+ *   split_budget(P, K) = (base, rest), split_thresh(P, t_1..t_L) = (base, rest):
+ *     two standard payloads with P's header fields (W, H, D, ncoeff / -L).
+ *     base is exactly thin_budget(P, K), respectively thin_thresh(P, t): the same
+ *     bytes, kept count, T and per-level thresholds.  rest holds the pairs of
+ *     canon(P) that are not in base, in position order, runs recomputed by the
+ *     reference's run rule: in the budget form the candidates with key <= T (ties
+ *     at T included), in the threshold form the candidates with |c| <= t_lvl.
+ *   Consequences: the positions of base and rest are disjoint; pairs(base) +
+ *     pairs(rest) = pairs(canon(P)); split(rest, K2) yields the next layer; the
+ *     first j layers together are the candidates with key above the j-th T.
+ *   merge(a, b), a and b standard payloads of the same unit and the same L: the
+ *     standard payload with that header whose pairs are all pairs of a and of b at
+ *     positions below N, in position order, value bits verbatim (nothing is
+ *     dropped for being +-0 or NaN), runs recomputed.  A pair of a and a pair of
+ *     b at the same position below N: the unit is refused (WC_ERR_FORMAT); layers
+ *     are disjoint by construction, there is no override or sum semantic.
+ *   Consequences: A(merge(a, b)) = A(a) + A(b) exactly; merge is commutative and
+ *     associative; merge(a, empty) = a without its pairs past N;
+ *     merge(split(P)) == canon(P) byte for byte, hence == P for every P an encoder
+ *     emitted; merge(a, b) has at most 20 + 8 min(N, pairs(a) + pairs(b)) bytes.
+ * Packed units are refused (WC_ERR_FORMAT): wc_unpack first.  Unit shapes: those
+ * wc_forward_levels accepts.
+ *
+ *   wc_split_unit / wc_merge_unit: host-only, no device; the rule on one unit.
+ *     wc_split_unit takes exactly one of max_pairs (K) and thresh (levels floats);
+ *     key and thresh_out are nullable, as in wc_thin_unit.  A header that is not a
+ *     standard one, a negative run, headers of a and b that differ (box or L), or
+ *     an overlap: WC_ERR_FORMAT.  A short input or output buffer: WC_ERR_INVALID.
+ *     Nothing is written on either.
+ *   wc_split_bound: the output extents of the split's device forms.  The base's
+ *     is wc_thin_bound's; unit u's rest slot is the prefix, starting at 4, of
+ *     24 + 8 N_u (wc_payload_bound's layout: the pair count of a payload is not
+ *     known to the host).  wc_merge_bound = wc_payload_bound.
+ *   wc_split_budget / wc_split_thresh: payloads at d_payload + d_offsets[u]
+ *     (multiples of 4) -> slots in d_base and d_rest (16-B aligned); d_base_offsets
+ *     and d_rest_offsets (n + 1), d_kept and d_rest_pairs (n): device.  d_thresh,
+ *     d_key: device, nullable.  levels, max_pairs, thresh: HOST, consumed before
+ *     the call returns.  Asynchronous on the context's stream; nothing is read back
+ *     between the passes; nothing is left staged.  The outputs must not overlap
+ *     the input or each other.  Scratch of the context: 16 B per coefficient the
+ *     units can hold, in tiles of 4096 (the thinning's 12 B and the rest's
+ *     positions).
+ *   wc_merge: payloads at d_a + d_a_offsets[u] and d_b + d_b_offsets[u] -> slots
+ *     in d_out, d_out_offsets (n + 1), d_pairs (n).  d_a and d_b may be the same
+ *     buffer with different offsets; the output must not overlap either input.
+ *     Scratch: 8 B per coefficient the units can hold, in tiles of 4096.
+ *   Errors of the device forms.  A capacity below the bound, or an output that
+ *     starts inside an input's or another output's extent: WC_ERR_INVALID, nothing
+ *     launched.  A header that disagrees with the unit (box, levels, a packed tag,
+ *     an offset that is no multiple of 4; for wc_merge either input's, so headers
+ *     of a and b that differ): WC_ERR_FORMAT at the next wc_synchronize, that
+ *     unit's slots stay untouched and its counts are 0, the other units are
+ *     processed.  A negative run: as in thinning.  An overlap in wc_merge:
+ *     WC_ERR_FORMAT at the next wc_synchronize, that unit's output is a header with
+ *     0 pairs and d_pairs[u] = 0, bytes past the header are unspecified but inside
+ *     its slot, the other units are merged.
+ *   _host forms: host buffers, results packed densely as wc_forward_host's
+ *     (capacities >= the bounds), levels NULL reads the headers, a header (for
+ *     wc_merge_host a header pair) that disagrees fails the call (WC_ERR_FORMAT)
+ *     before anything runs.  The unit runs (WC_OPT_HOST_CHUNK) go one after
+ *     another. */
+int wc_split_unit(const uint8_t* payload, size_t len, const uint32_t* max_pairs, const float* thresh, uint8_t* base,
+                  size_t base_cap, size_t* base_len, uint8_t* rest, size_t rest_cap, size_t* rest_len, uint32_t* key,
+                  float* thresh_out);
+int wc_merge_unit(const uint8_t* a, size_t a_len, const uint8_t* b, size_t b_len, uint8_t* out, size_t cap,
+                  size_t* written);
+int wc_split_bound(const wc_unit* units, int n, const uint32_t* max_pairs, uint64_t* base_bytes, uint64_t* rest_bytes);
+uint64_t wc_merge_bound(const wc_unit* units, int n);
+int wc_split_budget(wc_ctx* ctx, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                    const int32_t* levels, const uint32_t* max_pairs, uint8_t* d_base, uint64_t base_capacity,
+                    uint64_t* d_base_offsets, uint32_t* d_kept, uint8_t* d_rest, uint64_t rest_capacity,
+                    uint64_t* d_rest_offsets, uint32_t* d_rest_pairs, float* d_thresh, uint32_t* d_key);
+int wc_split_thresh(wc_ctx* ctx, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                    const int32_t* levels, const float* thresh, uint8_t* d_base, uint64_t base_capacity,
+                    uint64_t* d_base_offsets, uint32_t* d_kept, uint8_t* d_rest, uint64_t rest_capacity,
+                    uint64_t* d_rest_offsets, uint32_t* d_rest_pairs);
+int wc_merge(wc_ctx* ctx, const uint8_t* d_a, const uint64_t* d_a_offsets, const uint8_t* d_b,
+             const uint64_t* d_b_offsets, const wc_unit* units, int n, const int32_t* levels, uint8_t* d_out,
+             uint64_t out_capacity, uint64_t* d_out_offsets, uint32_t* d_pairs);
+int wc_split_budget_host(wc_ctx* ctx, const uint8_t* payload, const uint64_t* offsets, const wc_unit* units, int n,
+                         const int32_t* levels, const uint32_t* max_pairs, uint8_t* base, uint64_t base_capacity,
+                         uint64_t* base_offsets, uint32_t* kept, uint8_t* rest, uint64_t rest_capacity,
+                         uint64_t* rest_offsets, uint32_t* rest_pairs, float* thresh, uint32_t* key);
+int wc_split_thresh_host(wc_ctx* ctx, const uint8_t* payload, const uint64_t* offsets, const wc_unit* units, int n,
+                         const int32_t* levels, const float* thresh, uint8_t* base, uint64_t base_capacity,
+                         uint64_t* base_offsets, uint32_t* kept, uint8_t* rest, uint64_t rest_capacity,
+                         uint64_t* rest_offsets, uint32_t* rest_pairs);
+int wc_merge_host(wc_ctx* ctx, const uint8_t* a, const uint64_t* a_offsets, const uint8_t* b, const uint64_t* b_offsets,
+                  const wc_unit* units, int n, const int32_t* levels, uint8_t* out, uint64_t out_capacity,
+                  uint64_t* out_offsets, uint32_t* pairs);
+
 /* Opt-in reduced-resolution decode (not in the reference): the box at 1/2^r
  * resolution straight from a payload, without the work of the full resolution.
  * The low-pass corner of the coefficient array after undoing levels L..r+1 is
@@ -1003,7 +1105,8 @@ int wc_decompose_host(wc_ctx* ctx, const void* cells, int dtype, const wc_unit* 
 #define WC_STAGE_PAIRS 6      /* header check + pair counts of wc_inverse_rows with a caller row index */
 #define WC_STAGE_TOL 7        /* per-unit bins + threshold pick of the RMSE-tolerance mode (wc_forward_tol); per-level bins, pick
                                  and mask pass of wc_forward_levels_tol; radix select and mask pass of
-                                 wc_forward_levels_budget; every pass of wc_thin_budget / wc_thin_thresh */
+                                 wc_forward_levels_budget; every pass of wc_thin_budget / wc_thin_thresh, of
+                                 wc_split_budget / wc_split_thresh and of wc_merge */
 #define WC_STAGE_LEVELS 8    /* level passes, key pass and header patch of the multi-level mode (wc_forward_levels,
                                  wc_inverse_levels) */
 #define WC_STAGE_PACK 9      /* packed payloads: k_pack_widths + k_pack_body (wc_pack), k_unpack (wc_unpack) */

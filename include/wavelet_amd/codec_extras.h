@@ -85,6 +85,21 @@ std::vector<CompressedWavelet> compress_budget(multiBox3D& box, std::vector<int>
 std::vector<CompressedWavelet> thin_budget(const std::vector<CompressedWavelet>& compressed, double ratio);
 std::vector<CompressedWavelet> thin_thresh(const std::vector<CompressedWavelet>& compressed, float thresh);
 
+// Progressive layers in the compressed domain (GPU, wc_split_budget_host /
+// wc_split_thresh_host / wc_merge_host; not in the reference).  split_*: base[i] is
+// exactly thin_budget's / thin_thresh's struct for compressed[i]; rest[i] holds every
+// other non-zero, non-NaN coefficient of it, so that merge(base, rest) is the struct
+// again (byte for byte when serialized, for every struct an encoder of this project
+// made).  Splitting `rest` again yields the next layer.  merge: the union of a[i]
+// and b[i]; two layers of one component that hold a coefficient at the same position
+// exit with the library's message.  Nothing is written to disk.
+struct Layers {
+    std::vector<CompressedWavelet> base, rest;
+};
+Layers split_budget(const std::vector<CompressedWavelet>& compressed, double ratio);
+Layers split_thresh(const std::vector<CompressedWavelet>& compressed, float thresh);
+std::vector<CompressedWavelet> merge(const std::vector<CompressedWavelet>& a, const std::vector<CompressedWavelet>& b);
+
 // compress() whose files hold packed units (GPU, wc_pack_host after the forward; not
 // a reference format, include/wavelet_amd.h "Opt-in packed payloads"): each kept
 // value stored in its top `vbytes` bytes (4: lossless; 3, 2: rounded to nearest even,

@@ -12,7 +12,7 @@ from .capi import Context, WaveletError, make_units  # noqa: F401
 from .codec import (  # noqa: F401
     CompressedWavelet, calc_adj_loss, calc_rmse_per_box, calc_size, compress, compress_payloads,
     decompress, decompress_payloads, deserialize_compressed_wavelet, inverse_wavelet_decompose,
-    serialize_compressed_wavelet, thin_payloads, wavelet_decompose,
+    merge_payloads, serialize_compressed_wavelet, split_payloads, thin_payloads, wavelet_decompose,
 )
 
 __version__ = "0.1.0"

@@ -42,6 +42,8 @@ EXPORTED = (
     "wc_inverse_packed", "wc_inverse_packed_coarse", "wc_inverse_packed_region",
     "wc_inverse_packed_host", "wc_inverse_packed_coarse_host", "wc_inverse_packed_region_host",
     "wc_thin_unit", "wc_thin_bound", "wc_thin_budget", "wc_thin_thresh", "wc_thin_budget_host", "wc_thin_thresh_host",
+    "wc_split_unit", "wc_merge_unit", "wc_split_bound", "wc_merge_bound", "wc_split_budget", "wc_split_thresh",
+    "wc_merge", "wc_split_budget_host", "wc_split_thresh_host", "wc_merge_host",
 )
 WC_MAX_LEVELS = 4  # levels of the opt-in multi-level transform (1 = the reference's codec)
 WC_PACK_MAX_CELLS = 1 << 21  # the largest unit wc_pack / wc_unpack take (the host rule has no limit)
@@ -192,6 +194,19 @@ def load_library() -> ctypes.CDLL:
         "wc_thin_thresh": (i32, [vp, vp, vp, up, i32, vp, vp, vp, u64, vp, vp]),
         "wc_thin_budget_host": (i32, [vp, vp, vp, up, i32, vp, vp, vp, u64, vp, vp, vp, vp]),
         "wc_thin_thresh_host": (i32, [vp, vp, vp, up, i32, vp, vp, vp, u64, vp, vp]),
+        "wc_split_unit": (i32, [vp, ctypes.c_size_t, vp, vp, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
+                                vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint32),
+                                vp]),
+        "wc_merge_unit": (i32, [vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t,
+                                ctypes.POINTER(ctypes.c_size_t)]),
+        "wc_split_bound": (i32, [up, i32, vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "wc_merge_bound": (u64, [up, i32]),
+        "wc_split_budget": (i32, [vp, vp, vp, up, i32, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp, vp]),
+        "wc_split_thresh": (i32, [vp, vp, vp, up, i32, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp]),
+        "wc_merge": (i32, [vp, vp, vp, vp, vp, up, i32, vp, vp, u64, vp, vp]),
+        "wc_split_budget_host": (i32, [vp, vp, vp, up, i32, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp, vp]),
+        "wc_split_thresh_host": (i32, [vp, vp, vp, up, i32, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp]),
+        "wc_merge_host": (i32, [vp, vp, vp, vp, vp, up, i32, vp, vp, u64, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -428,6 +443,42 @@ class Context:
         self._check(self._L.wc_thin_thresh(self._h, ctypes.c_void_p(d_payload), ctypes.c_void_p(d_offsets), units, n,
                                            lv.ctypes.data, t.ctypes.data, ctypes.c_void_p(d_out), int(capacity),
                                            ctypes.c_void_p(d_out_offsets), ctypes.c_void_p(d_kept)))
+
+    def split_budget(self, d_payload: int, d_offsets: int, units, n: int, levels, max_pairs, d_base: int,
+                     base_capacity: int, d_base_offsets: int, d_kept: int, d_rest: int, rest_capacity: int,
+                     d_rest_offsets: int, d_rest_pairs: int, d_thresh: int | None = None, d_key: int | None = None):
+        """wc_split_budget: standard payloads -> (base, rest): base is thin_budget's
+        output, rest the other candidates.  Slots as split_bound gives them."""
+        lv = _levels_array(levels, n)
+        k = _pairs_array(max_pairs, n)
+        self._check(self._L.wc_split_budget(self._h, ctypes.c_void_p(d_payload), ctypes.c_void_p(d_offsets), units, n,
+                                            lv.ctypes.data, k.ctypes.data, ctypes.c_void_p(d_base), int(base_capacity),
+                                            ctypes.c_void_p(d_base_offsets), ctypes.c_void_p(d_kept),
+                                            ctypes.c_void_p(d_rest), int(rest_capacity),
+                                            ctypes.c_void_p(d_rest_offsets), ctypes.c_void_p(d_rest_pairs),
+                                            ctypes.c_void_p(d_thresh or 0), ctypes.c_void_p(d_key or 0)))
+
+    def split_thresh(self, d_payload: int, d_offsets: int, units, n: int, levels, thresh, d_base: int,
+                     base_capacity: int, d_base_offsets: int, d_kept: int, d_rest: int, rest_capacity: int,
+                     d_rest_offsets: int, d_rest_pairs: int):
+        """wc_split_thresh: base is thin_thresh's output (thresh: n x WC_MAX_LEVELS host
+        floats), rest the candidates at or below their level's threshold."""
+        lv = _levels_array(levels, n)
+        t = _thin_thresh_array(thresh, n)
+        self._check(self._L.wc_split_thresh(self._h, ctypes.c_void_p(d_payload), ctypes.c_void_p(d_offsets), units, n,
+                                            lv.ctypes.data, t.ctypes.data, ctypes.c_void_p(d_base), int(base_capacity),
+                                            ctypes.c_void_p(d_base_offsets), ctypes.c_void_p(d_kept),
+                                            ctypes.c_void_p(d_rest), int(rest_capacity),
+                                            ctypes.c_void_p(d_rest_offsets), ctypes.c_void_p(d_rest_pairs)))
+
+    def merge(self, d_a: int, d_a_offsets: int, d_b: int, d_b_offsets: int, units, n: int, levels, d_out: int,
+              capacity: int, d_out_offsets: int, d_pairs: int):
+        """wc_merge: the union of two standard payloads per unit (disjoint positions).
+        wc_forward's slot layout (merge_bound)."""
+        lv = _levels_array(levels, n)
+        self._check(self._L.wc_merge(self._h, ctypes.c_void_p(d_a), ctypes.c_void_p(d_a_offsets), ctypes.c_void_p(d_b),
+                                     ctypes.c_void_p(d_b_offsets), units, n, lv.ctypes.data, ctypes.c_void_p(d_out),
+                                     int(capacity), ctypes.c_void_p(d_out_offsets), ctypes.c_void_p(d_pairs)))
 
     def decompose_levels(self, d_cells: int, dtype: int, units, n: int, levels, d_flat: int):
         lv = _levels_array(levels, n)
@@ -677,6 +728,52 @@ class Context:
                                                 None if lv is None else lv.ctypes.data, t.ctypes.data,
                                                 out.ctypes.data, cap, out_offsets.ctypes.data, kept.ctypes.data))
         return out, out_offsets, kept[:n], None, None
+
+    def split_host(self, payload: np.ndarray, offsets: np.ndarray, units, n: int, levels=None, max_pairs=None,
+                   thresh=None):
+        """wc_split_budget_host (max_pairs) or wc_split_thresh_host (thresh: n x
+        WC_MAX_LEVELS) -> (base, base_offsets, kept, rest, rest_offsets, rest_pairs, thresh
+        [n, WC_MAX_LEVELS] or None, key or None), both packed as forward_host."""
+        if (max_pairs is None) == (thresh is None):
+            raise ValueError("exactly one of max_pairs and thresh")
+        p = np.ascontiguousarray(payload, np.uint8)
+        off = np.ascontiguousarray(offsets, np.uint64)
+        lv = None if levels is None else _levels_array(levels, n)
+        k = None if max_pairs is None else _pairs_array(max_pairs, n)
+        bcap, rcap = split_bound(units, n, k)
+        base, rest = np.empty(bcap, np.uint8), np.empty(rcap, np.uint8)
+        boff, roff = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
+        kept, rpairs = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        lvp = None if lv is None else lv.ctypes.data
+        if k is not None:
+            th = np.zeros((max(n, 1), WC_MAX_LEVELS), np.float32)
+            key = np.zeros(max(n, 1), np.uint32)
+            self._check(self._L.wc_split_budget_host(self._h, p.ctypes.data, off.ctypes.data, units, n, lvp,
+                                                     k.ctypes.data, base.ctypes.data, bcap, boff.ctypes.data,
+                                                     kept.ctypes.data, rest.ctypes.data, rcap, roff.ctypes.data,
+                                                     rpairs.ctypes.data, th.ctypes.data, key.ctypes.data))
+            return base, boff, kept[:n], rest, roff, rpairs[:n], th[:n], key[:n]
+        t = _thin_thresh_array(thresh, n)
+        self._check(self._L.wc_split_thresh_host(self._h, p.ctypes.data, off.ctypes.data, units, n, lvp, t.ctypes.data,
+                                                 base.ctypes.data, bcap, boff.ctypes.data, kept.ctypes.data,
+                                                 rest.ctypes.data, rcap, roff.ctypes.data, rpairs.ctypes.data))
+        return base, boff, kept[:n], rest, roff, rpairs[:n], None, None
+
+    def merge_host(self, a: np.ndarray, a_offsets: np.ndarray, b: np.ndarray, b_offsets: np.ndarray, units, n: int,
+                   levels=None):
+        """wc_merge_host -> (out, out_offsets, pairs), packed as forward_host.  levels None:
+        from the headers."""
+        pa, pb = np.ascontiguousarray(a, np.uint8), np.ascontiguousarray(b, np.uint8)
+        oa, ob = np.ascontiguousarray(a_offsets, np.uint64), np.ascontiguousarray(b_offsets, np.uint64)
+        lv = None if levels is None else _levels_array(levels, n)
+        cap = merge_bound(units, n)
+        out = np.empty(cap, np.uint8)
+        out_offsets = np.zeros(n + 1, np.uint64)
+        pairs = np.zeros(max(n, 1), np.uint32)
+        self._check(self._L.wc_merge_host(self._h, pa.ctypes.data, oa.ctypes.data, pb.ctypes.data, ob.ctypes.data,
+                                          units, n, None if lv is None else lv.ctypes.data, out.ctypes.data, cap,
+                                          out_offsets.ctypes.data, pairs.ctypes.data))
+        return out, out_offsets, pairs[:n]
 
     def forward_levels_host(self, cells: np.ndarray, units, n: int, levels, keep: float,
                             thresh: float | None = None):
@@ -1103,6 +1200,55 @@ def thin_unit(payload, max_pairs=None, thresh=None):
     if rc != 0:
         raise WaveletError(rc, "wc_thin_unit: refused")
     return out[:written.value].tobytes(), int(key.value), tout[:payload_levels(bytes(payload[:20]))].copy()
+
+
+def split_bound(units, n: int, max_pairs=None):
+    """wc_split_bound -> (base bytes, rest bytes) of split_budget (max_pairs) / split_thresh (None)."""
+    k = None if max_pairs is None else _pairs_array(max_pairs, n)
+    b, r = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rc = load_library().wc_split_bound(units, n, None if k is None else k.ctypes.data, ctypes.byref(b), ctypes.byref(r))
+    if rc:
+        raise WaveletError(rc, "wc_split_bound: invalid argument")
+    return int(b.value), int(r.value)
+
+
+def merge_bound(units, n: int) -> int:
+    """wc_merge_bound: the output extent of merge (= payload_bound)."""
+    return int(load_library().wc_merge_bound(units, n))
+
+
+def split_unit(payload, max_pairs=None, thresh=None, base_cap=None, rest_cap=None):
+    """wc_split_unit (host only): the rule on one standard payload -> (base bytes, rest
+    bytes, T, fp32 thresholds of levels 1..L).  Exactly one of max_pairs (K) and thresh."""
+    p = np.frombuffer(bytes(payload), np.uint8)
+    base = np.empty(max(p.size, 20) if base_cap is None else max(int(base_cap), 1), np.uint8)
+    rest = np.empty(max(p.size, 20) if rest_cap is None else max(int(rest_cap), 1), np.uint8)
+    bl, rl = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    key = ctypes.c_uint32(0)
+    tout = np.zeros(WC_MAX_LEVELS, np.float32)
+    k = None if max_pairs is None else ctypes.c_uint32(int(max_pairs))
+    t = None if thresh is None else np.ascontiguousarray(np.resize(np.asarray(thresh, np.float32), WC_MAX_LEVELS))
+    rc = load_library().wc_split_unit(p.ctypes.data, p.size, None if k is None else ctypes.addressof(k),
+                                      None if t is None else t.ctypes.data, base.ctypes.data,
+                                      base.size if base_cap is None else int(base_cap), ctypes.byref(bl),
+                                      rest.ctypes.data, rest.size if rest_cap is None else int(rest_cap),
+                                      ctypes.byref(rl), ctypes.byref(key), tout.ctypes.data)
+    if rc != 0:
+        raise WaveletError(rc, "wc_split_unit: refused")
+    return (base[:bl.value].tobytes(), rest[:rl.value].tobytes(), int(key.value),
+            tout[:payload_levels(bytes(payload[:20]))].copy())
+
+
+def merge_unit(a, b, cap=None):
+    """wc_merge_unit (host only): the union of two standard payloads of one unit -> bytes."""
+    pa, pb = np.frombuffer(bytes(a), np.uint8), np.frombuffer(bytes(b), np.uint8)
+    out = np.empty(max(pa.size + pb.size, 20) if cap is None else max(int(cap), 1), np.uint8)
+    written = ctypes.c_size_t(0)
+    rc = load_library().wc_merge_unit(pa.ctypes.data, pa.size, pb.ctypes.data, pb.size, out.ctypes.data,
+                                      out.size if cap is None else int(cap), ctypes.byref(written))
+    if rc != 0:
+        raise WaveletError(rc, "wc_merge_unit: refused")
+    return out[:written.value].tobytes()
 
 
 def budget_thresholds(key: int, levels: int):

@@ -175,26 +175,12 @@ def _standard_payloads(payloads: Sequence[bytes], device: int = 0) -> List[bytes
     return out
 
 
-def thin_payloads(payloads: Sequence[bytes], max_bytes=None, ratio=None, thresh=None, device: int = 0) -> List[bytes]:
-    """Payloads -> smaller payloads in the compressed domain (not in the reference;
-    wc_thin_budget_host / wc_thin_thresh_host): no cell and no dense coefficient
-    exists in between, and the result is what the forward's selection gives on the
-    array the payload decodes to.  max_bytes (an int or one per payload) and ratio
-    map to a pair budget exactly as in compress_payloads: each result keeps its
-    (max_bytes - 20) // 8 largest weighted coefficients and never more (ties at the
-    boundary are all dropped); ratio: max_bytes = max(20, floor(4 * N / ratio)) for
-    a box of N cells.  thresh (one float >= 0, or L per payload): keeps |c| > thresh
-    on every level (or thresh[i][lvl - 1]).  Exactly one of the three.  The levels
-    come from the headers.  Packed units are unpacked first; the results are
-    standard payloads."""
+def _selection(dims, n, max_bytes, ratio, thresh):
+    """thin_payloads' and split_payloads' arguments -> (pair budgets or None, n x WC_MAX_LEVELS thresholds or None)."""
     if sum(v is not None for v in (max_bytes, ratio, thresh)) != 1:
         raise ValueError("exactly one of max_bytes, ratio and thresh")
-    if not payloads:
-        return []
-    std = _standard_payloads(payloads, device)
-    dims = _header_dims(std)
-    units, n, _ = capi.make_units(dims)
-    buf, offsets = _laid_out(std)
+    if n == 0:
+        return None, None
     pairs = th = None
     if thresh is not None:
         th = np.zeros((n, capi.WC_MAX_LEVELS), np.float32)
@@ -219,8 +205,74 @@ def thin_payloads(payloads: Sequence[bytes], max_bytes=None, ratio=None, thresh=
             if any(v < 20 for v in budget):
                 raise ValueError("max_bytes: a payload's header alone takes 20 bytes")
         pairs = [min((v - 20) // 8, 0xFFFFFFFF) for v in budget]
+    return pairs, th
+
+
+def thin_payloads(payloads: Sequence[bytes], max_bytes=None, ratio=None, thresh=None, device: int = 0) -> List[bytes]:
+    """Payloads -> smaller payloads in the compressed domain (not in the reference;
+    wc_thin_budget_host / wc_thin_thresh_host): no cell and no dense coefficient
+    exists in between, and the result is what the forward's selection gives on the
+    array the payload decodes to.  max_bytes (an int or one per payload) and ratio
+    map to a pair budget exactly as in compress_payloads: each result keeps its
+    (max_bytes - 20) // 8 largest weighted coefficients and never more (ties at the
+    boundary are all dropped); ratio: max_bytes = max(20, floor(4 * N / ratio)) for
+    a box of N cells.  thresh (one float >= 0, or L per payload): keeps |c| > thresh
+    on every level (or thresh[i][lvl - 1]).  Exactly one of the three.  The levels
+    come from the headers.  Packed units are unpacked first; the results are
+    standard payloads."""
+    if not payloads:
+        _selection([], 0, max_bytes, ratio, thresh)
+        return []
+    std = _standard_payloads(payloads, device)
+    dims = _header_dims(std)
+    units, n, _ = capi.make_units(dims)
+    buf, offsets = _laid_out(std)
+    pairs, th = _selection(dims, n, max_bytes, ratio, thresh)
     out, off, kept = context(device).thin_host(buf, offsets, units, n, None, max_pairs=pairs, thresh=th)[:3]
     return [capi.unit_payload(out, off, kept, i) for i in range(n)]
+
+
+def split_payloads(payloads: Sequence[bytes], max_bytes=None, ratio=None, thresh=None, device: int = 0):
+    """Payloads -> (bases, rests) in the compressed domain (not in the reference;
+    wc_split_budget_host / wc_split_thresh_host).  bases[i] is exactly what
+    thin_payloads gives with the same arguments; rests[i] holds every other
+    candidate of the payload (its non-zero, non-NaN coefficients), so that
+    merge_payloads(bases, rests) is the payload again, byte for byte, for every
+    payload an encoder of this project emitted.  Splitting rests[i] again yields the
+    next layer.  Packed units are unpacked first; the results are standard payloads."""
+    if not payloads:
+        _selection([], 0, max_bytes, ratio, thresh)
+        return [], []
+    std = _standard_payloads(payloads, device)
+    dims = _header_dims(std)
+    units, n, _ = capi.make_units(dims)
+    buf, offsets = _laid_out(std)
+    pairs, th = _selection(dims, n, max_bytes, ratio, thresh)
+    base, boff, kept, rest, roff, rpairs = context(device).split_host(buf, offsets, units, n, None, max_pairs=pairs,
+                                                                      thresh=th)[:6]
+    return ([capi.unit_payload(base, boff, kept, i) for i in range(n)],
+            [capi.unit_payload(rest, roff, rpairs, i) for i in range(n)])
+
+
+def merge_payloads(a: Sequence[bytes], b: Sequence[bytes], *more: Sequence[bytes], device: int = 0) -> List[bytes]:
+    """Layers -> their union in the compressed domain (not in the reference;
+    wc_merge_host): result[i] holds every pair of a[i], b[i] and more[j][i].  The
+    layers of one unit must not hold a pair at the same position (WaveletError,
+    WC_ERR_FORMAT).  Folds pairwise, left to right.  Packed units are unpacked first."""
+    out = list(a)
+    for nxt in (b,) + more:
+        if len(nxt) != len(out):
+            raise ValueError("merge_payloads: every argument holds one payload per unit")
+        if not out:
+            continue
+        sa, sb = _standard_payloads(out, device), _standard_payloads(nxt, device)
+        dims = _header_dims(sa)
+        units, n, _ = capi.make_units(dims)
+        ba, oa = _laid_out(sa)
+        bb, ob = _laid_out(sb)
+        res, off, pairs = context(device).merge_host(ba, oa, bb, ob, units, n, None)
+        out = [capi.unit_payload(res, off, pairs, i) for i in range(n)]
+    return out
 
 
 def compress_payloads(boxes: Sequence[np.ndarray], keep: float, device: int = 0, levels: int = 1, rmse=None,

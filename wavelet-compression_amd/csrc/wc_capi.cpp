@@ -490,7 +490,8 @@ void wc_ctx_destroy(wc_ctx* c) {
                       &c->plan.d_rdtiles, &c->rowinfo,    &c->istate,        &c->npairs,
                       &c->tol_in,        &c->tol_bins,       &c->h_thresh,       &c->h_bound,
                       &c->lv_side,       &c->pk_desc,        &c->pk_in,          &c->pk_out,
-                      &c->pk_off,        &c->pk_bytes,       &c->thin};
+                      &c->pk_off,        &c->pk_bytes,       &c->thin,           &c->merge,
+                      &c->h_second,      &c->h_second_off,   &c->h_second_cnt};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (Plan& P : c->plan_cache) free_plan(P);
@@ -1414,18 +1415,26 @@ namespace wc {
 // tiles and their look-back granules; the call's descriptors and split layout go
 // through the pinned block.  Everything of wc_ctx::thin is sized and grown here,
 // before the first launch; the state words are cleared on the stream.
-int thin_device(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
-                const int32_t* levels, const uint32_t* max_pairs, const float* thresh, bool full_slots, uint8_t* d_out,
-                uint64_t out_capacity, uint64_t* d_out_offsets, uint32_t* d_kept, float* d_thresh, uint32_t* d_key) {
+// With `so` the call is a split (wc_layers.hip): the same descriptors, plan and scratch, the rest's slots
+// (wc_forward's layout), 4 B per coefficient more for the rest's positions, and launch_split.
+static int thin_or_split(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                         const int32_t* levels, const uint32_t* max_pairs, const float* thresh, bool full_slots,
+                         uint8_t* d_out, uint64_t out_capacity, uint64_t* d_out_offsets, uint32_t* d_kept,
+                         float* d_thresh, uint32_t* d_key, const SplitOut* so) {
     const bool budget = max_pairs != nullptr;
     int rc;
     if ((rc = validate_levels(c, units, n, levels))) return rc;
     std::vector<ThinDesc> desc(n);
-    uint64_t cursor = 4;
+    std::vector<uint64_t> rest_off(so ? n : 0);
+    uint64_t cursor = 4, rcursor = 4;
     for (int u = 0; u < n; ++u) {
         const wc_unit& f = units[u];
         const uint64_t N = (uint64_t)f.nx * f.ny * f.nz;
         const int L = levels[u];
+        if (so) {
+            rest_off[u] = rcursor;
+            rcursor += 24 + 8 * N;
+        }
         ThinDesc& d = desc[u];
         d = ThinDesc{};
         d.dmagic = N ? rows_magic(f.nz) : 0;
@@ -1450,10 +1459,19 @@ int thin_device(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, 
         cursor += 24 + 8ull * d.cap;
     }
     if (out_capacity < cursor) return fail(c, WC_ERR_INVALID, "out_capacity < wc_thin_bound");
+    if (so && so->capacity < rcursor) return fail(c, WC_ERR_INVALID, "rest_capacity < wc_split_bound");
     {  // the input's length is not known here: what can be seen is its start inside the output's extent
         const uintptr_t a0 = (uintptr_t)d_payload, a1 = a0 + 24, b0 = (uintptr_t)d_out, b1 = b0 + cursor;
         if (a0 < b1 && b0 < a1) return fail(c, WC_ERR_INVALID, "out overlaps the payload buffer");
+        if (so) {
+            const uintptr_t r0 = (uintptr_t)so->d_rest, r1 = r0 + rcursor;
+            if (a0 < r1 && r0 < a1) return fail(c, WC_ERR_INVALID, "rest overlaps the payload buffer");
+            if (b0 < r1 && r0 < b1) return fail(c, WC_ERR_INVALID, "base and rest overlap");
+        }
     }
+    if (so && ((rc = check_aligned(c, so->d_rest, "rest")) || (rc = check_aligned(c, so->d_offsets, "rest_offsets", 8)) ||
+               (rc = check_aligned(c, so->d_pairs, "rest_pairs", 4))))
+        return rc;
     if ((rc = check_aligned(c, d_payload, "payload")) || (rc = check_aligned(c, d_offsets, "offsets", 8)) ||
         (rc = check_aligned(c, d_out, "out")) || (rc = check_aligned(c, d_out_offsets, "out_offsets", 8)) ||
         (rc = check_aligned(c, d_kept, "kept", 4)) || (rc = check_aligned(c, d_thresh, "thresh", 4)) ||
@@ -1483,20 +1501,23 @@ int thin_device(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, 
         for (uint32_t t = 0; t < d.ndt; t += chunk) items.push_back(make_uint2((uint32_t)u, t));
     }
     const size_t nsplit = split.size(), nitems = items.size();
-    // the pinned blob: ThinDesc[n] | items[nitems] | split_units[nsplit]
+    // the pinned blob: ThinDesc[n] | items[nitems] | split_units[nsplit] | (a split) rest_off[n]
     const size_t o_items = sizeof(ThinDesc) * n, o_split = o_items + sizeof(uint2) * nitems,
-                 in_bytes = o_split + 4 * nsplit;
-    // wc_ctx::thin: [ticket[2][n] | keptw[n] | keyw[n] | status[2][tiles]] (cleared) | state[nsplit] | thresh[n][4] |
-    //               gbins[nsplit][4352] | s2[tiles * kFlatTile] | s1[tiles * kFlatTile]
-    const size_t o_status = round_up(16ull * n, 8), clear_bytes = o_status + 16ull * tiles,
+                 o_rest = round_up(o_split + 4 * nsplit, 8), in_bytes = so ? o_rest + 8ull * n : o_split + 4 * nsplit;
+    // wc_ctx::thin: [ticket[2][n] | keptw[n] | keyw[n] | (a split) restw[n] | status[2][tiles]] (cleared) |
+    //               state[nsplit] | thresh[n][4] | gbins[nsplit][4352] | s2[tiles * kFlatTile] |
+    //               s1[tiles * kFlatTile] | (a split) s3[tiles * kFlatTile]
+    const size_t o_status = round_up((so ? 20ull : 16ull) * n, 8), clear_bytes = o_status + 16ull * tiles,
                  o_state = round_up(clear_bytes, 16), o_th = o_state + sizeof(BudgetState) * nsplit,
                  o_bins = o_th + sizeof(float) * WC_MAX_LEVELS * n, o_s2 = o_bins + 4ull * 4352 * nsplit,
-                 o_s1 = round_up(o_s2 + 4ull * kFlatTile * tiles, 16), total = o_s1 + 8ull * kFlatTile * tiles;
+                 o_s1 = round_up(o_s2 + 4ull * kFlatTile * tiles, 16), o_s3 = o_s1 + 8ull * kFlatTile * tiles,
+                 total = o_s3 + (so ? 4ull * kFlatTile * tiles : 0);
     uint8_t* pin = nullptr;
     if ((rc = ensure(c, c->thin, total)) || (rc = pin_begin(c, in_bytes, in_bytes, &pin))) return rc;
     std::memcpy(pin, desc.data(), sizeof(ThinDesc) * n);
     if (nitems) std::memcpy(pin + o_items, items.data(), sizeof(uint2) * nitems);
     if (nsplit) std::memcpy(pin + o_split, split.data(), 4 * nsplit);
+    if (so) std::memcpy(pin + o_rest, rest_off.data(), 8ull * n);
     if ((rc = pin_upload(c, in_bytes))) return rc;
     uint8_t* s = (uint8_t*)c->thin.p;
     const uint8_t* blob = (const uint8_t*)c->tol_in.p;
@@ -1533,8 +1554,122 @@ int thin_device(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, 
     a.kept = d_kept;
     a.err = (uint32_t*)c->errflag.p;
     StageTimer t(c, WC_STAGE_TOL);
-    if ((e = launch_thin(c->stream, a)) != hipSuccess) return hip_fail(c, e, "thin launch");
+    if (so) {
+        SplitLaunch b{};
+        b.thin = a;
+        b.rest_off = (const uint64_t*)(blob + o_rest);
+        b.s3 = (uint32_t*)(s + o_s3);
+        b.restw = (uint32_t*)s + 4 * (size_t)n;
+        b.rest = so->d_rest;
+        b.rest_offsets = so->d_offsets;
+        b.rest_pairs = so->d_pairs;
+        if ((e = launch_split(c->stream, b)) != hipSuccess) return hip_fail(c, e, "split launch");
+    } else if ((e = launch_thin(c->stream, a)) != hipSuccess) {
+        return hip_fail(c, e, "thin launch");
+    }
     c->err_check_pending = true;  // malformed payloads surface at the next wc_synchronize
+    return WC_OK;
+}
+
+int thin_device(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                const int32_t* levels, const uint32_t* max_pairs, const float* thresh, bool full_slots, uint8_t* d_out,
+                uint64_t out_capacity, uint64_t* d_out_offsets, uint32_t* d_kept, float* d_thresh, uint32_t* d_key) {
+    return thin_or_split(c, d_payload, d_offsets, units, n, levels, max_pairs, thresh, full_slots, d_out, out_capacity,
+                         d_out_offsets, d_kept, d_thresh, d_key, nullptr);
+}
+
+int split_device(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                 const int32_t* levels, const uint32_t* max_pairs, const float* thresh, bool full_slots, uint8_t* d_base,
+                 uint64_t base_capacity, uint64_t* d_base_offsets, uint32_t* d_kept, const SplitOut& rest,
+                 float* d_thresh, uint32_t* d_key) {
+    return thin_or_split(c, d_payload, d_offsets, units, n, levels, max_pairs, thresh, full_slots, d_base, base_capacity,
+                         d_base_offsets, d_kept, d_thresh, d_key, &rest);
+}
+
+// wc_merge (wc_layers.hip).  The dense plan of the units gives the pair tiles of either input; the
+// descriptors go through the pinned block; wc_ctx::merge is sized and grown here, before the first launch.
+int merge_device(wc_ctx* c, const uint8_t* d_a, const uint64_t* d_a_offsets, const uint8_t* d_b,
+                 const uint64_t* d_b_offsets, const wc_unit* units, int n, const int32_t* levels, uint8_t* d_out,
+                 uint64_t out_capacity, uint64_t* d_out_offsets, uint32_t* d_pairs) {
+    int rc;
+    if ((rc = validate_levels(c, units, n, levels))) return rc;
+    std::vector<ThinDesc> desc(n);
+    uint64_t cursor = 4;
+    for (int u = 0; u < n; ++u) {
+        const wc_unit& f = units[u];
+        const uint64_t N = (uint64_t)f.nx * f.ny * f.nz;
+        ThinDesc& d = desc[u];
+        d = ThinDesc{};
+        d.W = f.nx;
+        d.H = f.ny;
+        d.D = f.nz;
+        d.want = levels[u] >= 2 ? -levels[u] : (int32_t)N;
+        d.N = (uint32_t)N;
+        d.L = (uint32_t)levels[u];
+        d.slot = kLtSolo;
+        d.cap = (uint32_t)N;
+        d.out_off = cursor;
+        cursor += 24 + 8 * N;
+    }
+    if (out_capacity < cursor) return fail(c, WC_ERR_INVALID, "out_capacity < wc_merge_bound");
+    for (const uint8_t* in : {d_a, d_b}) {  // an input's length is not known here: its start inside the output's extent
+        const uintptr_t a0 = (uintptr_t)in, a1 = a0 + 24, b0 = (uintptr_t)d_out, b1 = b0 + cursor;
+        if (a0 < b1 && b0 < a1) return fail(c, WC_ERR_INVALID, "out overlaps an input buffer");
+    }
+    if ((rc = check_aligned(c, d_a, "a")) || (rc = check_aligned(c, d_a_offsets, "a_offsets", 8)) ||
+        (rc = check_aligned(c, d_b, "b")) || (rc = check_aligned(c, d_b_offsets, "b_offsets", 8)) ||
+        (rc = check_aligned(c, d_out, "out")) || (rc = check_aligned(c, d_out_offsets, "out_offsets", 8)) ||
+        (rc = check_aligned(c, d_pairs, "pairs", 4)))
+        return rc;
+    if ((rc = set_device(c))) return rc;
+    std::vector<wc_unit> full(units, units + n);
+    for (wc_unit& u : full) u.cell_offset = 0;
+    const bool rows = c->opt_inv_rows;
+    c->opt_inv_rows = false;  // a dense plan: every unit's pair tiles in dtiles
+    rc = get_plan(c, full.data(), n);
+    c->opt_inv_rows = rows;
+    if (rc) return rc;
+    const Plan& P = c->plan;
+    uint64_t tiles = 0;
+    for (int u = 0; u < n; ++u) {
+        desc[u].dt_begin = P.units[u].dt_begin;
+        tiles += P.units[u].ndt;
+    }
+    // wc_ctx::merge: [ticket[2][n] | live[2][n] | overlap[n] | status[2][tiles]] (cleared) | pos[2][tiles * kFlatTile]
+    const size_t o_status = round_up(20ull * n, 8), clear_bytes = round_up(o_status + 16ull * tiles, 16),
+                 total = clear_bytes + 8ull * kFlatTile * tiles, in_bytes = sizeof(ThinDesc) * n;
+    uint8_t* pin = nullptr;
+    if ((rc = ensure(c, c->merge, total)) || (rc = pin_begin(c, in_bytes, in_bytes, &pin))) return rc;
+    std::memcpy(pin, desc.data(), in_bytes);
+    if ((rc = pin_upload(c, in_bytes))) return rc;
+    uint8_t* s = (uint8_t*)c->merge.p;
+    hipError_t e = hipMemsetAsync(s, 0, clear_bytes, c->stream);
+    if (e != hipSuccess) return hip_fail(c, e, "memset");
+    MergeLaunch a{};
+    a.desc = (const ThinDesc*)c->tol_in.p;
+    a.n = n;
+    a.tiles = (const FTile*)P.d_dtiles.p;
+    a.ntiles = (uint32_t)P.dtiles.size();
+    a.pay[0] = d_a;
+    a.pay[1] = d_b;
+    a.off[0] = d_a_offsets;
+    a.off[1] = d_b_offsets;
+    a.ordered = use_ordered(c) ? (c->opt_reverse ? 2 : 1) : 0;
+    a.ticket[0] = (uint32_t*)s;
+    a.ticket[1] = (uint32_t*)s + n;
+    a.live = (uint32_t*)s + 2 * (size_t)n;
+    a.overlap = (uint32_t*)s + 4 * (size_t)n;
+    a.status[0] = (unsigned long long*)(s + o_status);
+    a.status[1] = a.status[0] + tiles;
+    a.pos[0] = (uint32_t*)(s + clear_bytes);
+    a.pos[1] = a.pos[0] + (size_t)kFlatTile * tiles;
+    a.out = d_out;
+    a.out_offsets = d_out_offsets;
+    a.pairs = d_pairs;
+    a.err = (uint32_t*)c->errflag.p;
+    StageTimer t(c, WC_STAGE_TOL);
+    if ((e = launch_merge(c->stream, a)) != hipSuccess) return hip_fail(c, e, "merge launch");
+    c->err_check_pending = true;  // malformed payloads and overlaps surface at the next wc_synchronize
     return WC_OK;
 }
 
@@ -1562,6 +1697,52 @@ int wc_thin_budget(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offset
         return fail(c, WC_ERR_INVALID, "null buffer");
     return thin_device(c, d_payload, d_offsets, units, n, levels, max_pairs, nullptr, false, d_out, out_capacity,
                        d_out_offsets, d_kept, d_thresh, d_key);
+}
+
+// Progressive layers (wc_layers.hip): a payload into (base, rest), and two payloads into their union.
+int wc_split_budget(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                    const int32_t* levels, const uint32_t* max_pairs, uint8_t* d_base, uint64_t base_capacity,
+                    uint64_t* d_base_offsets, uint32_t* d_kept, uint8_t* d_rest, uint64_t rest_capacity,
+                    uint64_t* d_rest_offsets, uint32_t* d_rest_pairs, float* d_thresh, uint32_t* d_key) {
+    if (!c) return WC_ERR_INVALID;
+    int rc;
+    if ((rc = validate_units(c, units, n))) return rc;
+    if (n == 0) return WC_OK;
+    if (!d_payload || !d_offsets || !levels || !max_pairs || !d_base || !d_base_offsets || !d_kept || !d_rest ||
+        !d_rest_offsets || !d_rest_pairs)
+        return fail(c, WC_ERR_INVALID, "null buffer");
+    return split_device(c, d_payload, d_offsets, units, n, levels, max_pairs, nullptr, false, d_base, base_capacity,
+                        d_base_offsets, d_kept, SplitOut{d_rest, rest_capacity, d_rest_offsets, d_rest_pairs}, d_thresh,
+                        d_key);
+}
+
+int wc_split_thresh(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                    const int32_t* levels, const float* thresh, uint8_t* d_base, uint64_t base_capacity,
+                    uint64_t* d_base_offsets, uint32_t* d_kept, uint8_t* d_rest, uint64_t rest_capacity,
+                    uint64_t* d_rest_offsets, uint32_t* d_rest_pairs) {
+    if (!c) return WC_ERR_INVALID;
+    int rc;
+    if ((rc = validate_units(c, units, n))) return rc;
+    if (n == 0) return WC_OK;
+    if (!d_payload || !d_offsets || !levels || !thresh || !d_base || !d_base_offsets || !d_kept || !d_rest ||
+        !d_rest_offsets || !d_rest_pairs)
+        return fail(c, WC_ERR_INVALID, "null buffer");
+    return split_device(c, d_payload, d_offsets, units, n, levels, nullptr, thresh, false, d_base, base_capacity,
+                        d_base_offsets, d_kept, SplitOut{d_rest, rest_capacity, d_rest_offsets, d_rest_pairs}, nullptr,
+                        nullptr);
+}
+
+int wc_merge(wc_ctx* c, const uint8_t* d_a, const uint64_t* d_a_offsets, const uint8_t* d_b, const uint64_t* d_b_offsets,
+             const wc_unit* units, int n, const int32_t* levels, uint8_t* d_out, uint64_t out_capacity,
+             uint64_t* d_out_offsets, uint32_t* d_pairs) {
+    if (!c) return WC_ERR_INVALID;
+    int rc;
+    if ((rc = validate_units(c, units, n))) return rc;
+    if (n == 0) return WC_OK;
+    if (!d_a || !d_a_offsets || !d_b || !d_b_offsets || !levels || !d_out || !d_out_offsets || !d_pairs)
+        return fail(c, WC_ERR_INVALID, "null buffer");
+    return merge_device(c, d_a, d_a_offsets, d_b, d_b_offsets, units, n, levels, d_out, out_capacity, d_out_offsets,
+                        d_pairs);
 }
 
 int wc_thin_thresh(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,

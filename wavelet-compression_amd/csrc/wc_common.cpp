@@ -107,6 +107,7 @@ int check_kernel_errors(wc_ctx* c) {
         std::snprintf(buf, sizeof buf, "malformed payload (flags 0x%x: 1 header, 2 negative run)", flag);
         return fail(c, WC_ERR_FORMAT, buf);
     }
+    if (flag & kErrOverlap) return fail(c, WC_ERR_FORMAT, "wc_merge: the inputs of a unit hold a pair at the same position");
     return WC_OK;
 }
 

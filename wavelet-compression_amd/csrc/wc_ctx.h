@@ -39,6 +39,10 @@
 //   wc_thinrule.cpp / wc_thinhost.cpp  thinning in the compressed domain: the rule on
 //                    one payload (wc_thin_unit, plain C++), wc_thin_bound and the
 //                    _host forms of wc_thin_budget / wc_thin_thresh (payload_serial)
+//   wc_layersrule.cpp / wc_layershost.cpp  progressive layers: the rule on one unit
+//                    (wc_split_unit, wc_merge_unit, plain C++, on wc_thin_unit), the bounds and
+//                    the _host forms of wc_split_budget / wc_split_thresh / wc_merge
+//                    (payload_serial with its second stream)
 //   wc_coarsehost.cpp host side of the reduced-resolution inverse: wc_coarse_units,
 //                    the argument checks and wc_inverse_coarse_host (a call of
 //                    wc_regionhost.cpp's inverse_compact_host)
@@ -144,6 +148,11 @@ hipError_t launch_unpack_units(hipStream_t, const PackDesc*, const FTile* tiles,
 
 // wc_thin.hip: the passes of wc_thin_budget / wc_thin_thresh (wc_internal.h ThinLaunch)
 hipError_t launch_thin(hipStream_t, const ThinLaunch&);
+// its scan and select alone (the front of wc_split_budget)
+hipError_t launch_thin_front(hipStream_t, const ThinLaunch&);
+// wc_layers.hip: the passes of wc_split_budget / wc_split_thresh and of wc_merge
+hipError_t launch_split(hipStream_t, const SplitLaunch&);
+hipError_t launch_merge(hipStream_t, const MergeLaunch&);
 
 struct DevBuf {
     void* p = nullptr;
@@ -275,6 +284,9 @@ struct wc_ctx {
     wc::DevBuf pk_in, pk_out, pk_off, pk_bytes;
     // wc_thin_budget / wc_thin_thresh: per-call state, select bins and the two pair scratches (wc_thin.hip)
     wc::DevBuf thin;
+    // wc_merge: per-call state and the two position rows (wc_layers.hip).  payload_serial's second stream:
+    // a split's rest slots with their offsets and counts, or a merge's second input with its offsets
+    wc::DevBuf merge, h_second, h_second_off, h_second_cnt;
     std::unique_ptr<wc::HostPool> hpool;
     // uploads from pageable host memory: copied by upool's threads into pinned
     // bounce slots, each slot's copy to the device ordered by an event
@@ -366,6 +378,18 @@ struct SerialOut {
     uint64_t* out_offsets = nullptr;
     uint32_t* kept = nullptr;
     std::vector<UnitResult> results;
+    // the layers' second stream (wc_layershost.cpp); both unset for every other caller.
+    // A second packed output (a split's rest; payload set too): the step left the run's slots, wc_forward's
+    // layout, in c->h_second (of the run's wc_payload_bound) and their counts in c->h_second_cnt.
+    uint8_t* payload2 = nullptr;
+    uint64_t cap2 = 0;
+    uint64_t* out_offsets2 = nullptr;
+    uint32_t* kept2 = nullptr;
+    // A second input (a merge's b): unit u's bytes [offsets2[u], end2[u]) of bytes2 go up with the run, to
+    // c->h_second at the same shift rule, their rebased offsets to c->h_second_off.
+    const uint8_t* bytes2 = nullptr;
+    const uint64_t* offsets2 = nullptr;
+    const uint64_t* end2 = nullptr;
 };
 // unit u's bytes are [offsets[u], end[u]); runs are split by the cells of units
 int payload_serial(wc_ctx* c, const uint8_t* bytes, const uint64_t* offsets, const uint64_t* end, const wc_unit* units,
@@ -395,6 +419,22 @@ int validate_pack(wc_ctx* c, const wc_unit* units, int n);
 int thin_device(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
                 const int32_t* levels, const uint32_t* max_pairs, const float* thresh, bool full_slots, uint8_t* d_out,
                 uint64_t out_capacity, uint64_t* d_out_offsets, uint32_t* d_kept, float* d_thresh, uint32_t* d_key);
+
+// wc_capi.cpp: wc_split_budget / wc_split_thresh and wc_merge after their null checks (thin_device's
+// conventions; full_slots: the base in wc_forward's slot layout).
+struct SplitOut {  // the rest's side of a split
+    uint8_t* d_rest;
+    uint64_t capacity;
+    uint64_t* d_offsets;
+    uint32_t* d_pairs;
+};
+int split_device(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                 const int32_t* levels, const uint32_t* max_pairs, const float* thresh, bool full_slots, uint8_t* d_base,
+                 uint64_t base_capacity, uint64_t* d_base_offsets, uint32_t* d_kept, const SplitOut& rest,
+                 float* d_thresh, uint32_t* d_key);
+int merge_device(wc_ctx* c, const uint8_t* d_a, const uint64_t* d_a_offsets, const uint8_t* d_b,
+                 const uint64_t* d_b_offsets, const wc_unit* units, int n, const int32_t* levels, uint8_t* d_out,
+                 uint64_t out_capacity, uint64_t* d_out_offsets, uint32_t* d_pairs);
 
 // Bracket one launch with events when profiling is on.
 struct StageTimer {

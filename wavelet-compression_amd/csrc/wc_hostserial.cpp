@@ -7,7 +7,8 @@
 // full-size units) and take them one after another on the context's stream; they
 // are not pipelined over the copy streams as wc_forward_host is (wc_hostpipe.cpp).
 // forward_serial: cells in, packed payloads out.  payload_serial: payload bytes
-// in; the units' boxes or (thinning) packed payloads out.
+// in; the units' boxes or (thinning, layers) packed payloads out.  The layers add a
+// second stream to it: a second packed output (a split) or a second input (a merge).
 //
 // One rule on errors: after a driver's first enqueue every return goes through
 // serial_finish, which drains the stream first.  No copy that reads or writes
@@ -106,17 +107,19 @@ int ensure_pack_staging(wc_ctx* c, int run_units, uint64_t run_bound) {
 // Run [a, a + m), whose slots (wc_forward's layout, the plan's units) are at d_slots: pack them
 // densely (offsets stay == 4 mod 8, as wc_forward_host does); then the tail: the sizes and kept
 // counts back, the run's offsets rebased to R, its bytes to payload + R.
-hipError_t pack_run(wc_ctx* c, int m, const uint8_t* d_slots) {
-    return launch_pack(c->stream, (const UnitDev*)c->plan.d_units.p, m, (const uint32_t*)c->h_kept.p, d_slots,
-                       (uint64_t*)c->h_poff.p, (uint8_t*)c->h_packed.p);
+// (d_kept: the slots' pair counts; NULL: c->h_kept)
+hipError_t pack_run(wc_ctx* c, int m, const uint8_t* d_slots, const void* d_kept = nullptr) {
+    return launch_pack(c->stream, (const UnitDev*)c->plan.d_units.p, m, (const uint32_t*)(d_kept ? d_kept : c->h_kept.p),
+                       d_slots, (uint64_t*)c->h_poff.p, (uint8_t*)c->h_packed.p);
 }
 
 int packed_run_tail(wc_ctx* c, int a, int m, std::vector<uint64_t>& po, uint8_t* payload, uint64_t cap, uint64_t* offsets,
-                    uint32_t* kept, uint64_t& R) {
+                    uint32_t* kept, uint64_t& R, const void* d_kept = nullptr) {
     hipError_t e;
     if ((e = hipMemcpyAsync(po.data(), c->h_poff.p, sizeof(uint64_t) * (m + 1), hipMemcpyDeviceToHost, c->stream)) !=
             hipSuccess ||
-        (e = hipMemcpyAsync(kept + a, c->h_kept.p, 4ull * m, hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(kept + a, d_kept ? d_kept : c->h_kept.p, 4ull * m, hipMemcpyDeviceToHost, c->stream)) !=
+            hipSuccess ||
         (e = hipStreamSynchronize(c->stream)) != hipSuccess)
         return hip_fail(c, e, "sizes readback");
     for (int i = 0; i < m; ++i) offsets[a + i] = R - 4 + po[i];
@@ -208,19 +211,28 @@ int payload_serial(wc_ctx* c, const uint8_t* bytes, const uint64_t* offsets, con
     const std::vector<int> rb = serial_runs(c, units, n);
     const int nr = (int)rb.size() - 1;
     int run_units;
-    uint64_t run_bound, run_bytes = 0;
+    uint64_t run_bound, run_bytes = 0, run_bytes2 = 0;
     run_sizes(rb, units, run_units, run_bound);
     for (int r = 0; r < nr; ++r) {
         uint64_t lo, hi;
         byte_span(offsets, end, rb[r], rb[r + 1] - rb[r], lo, hi);
         run_bytes = std::max(run_bytes, hi - lo);
+        if (o.bytes2) {
+            byte_span(o.offsets2, o.end2, rb[r], rb[r + 1] - rb[r], lo, hi);
+            run_bytes2 = std::max(run_bytes2, hi - lo);
+        }
     }
+    if ((o.bytes2 || o.payload2) &&
+        ((rc = ensure(c, c->h_second, o.bytes2 ? run_bytes2 + o.slack : run_bound)) ||
+         (rc = ensure(c, c->h_second_off, sizeof(uint64_t) * (run_units + 1))) ||
+         (rc = ensure(c, c->h_second_cnt, 4ull * run_units))))
+        return rc;
     if ((rc = ensure(c, c->h_payload, run_bytes + o.slack)) || (rc = ensure(c, c->h_out, packs ? run_bound : o.out_bytes)) ||
         (rc = packs ? ensure_pack_staging(c, run_units, run_bound)
                     : ensure(c, c->h_offsets, sizeof(uint64_t) * run_units)))
         return rc;
-    std::vector<uint64_t> ro(run_units), po(packs ? run_units + 1 : 0);
-    uint64_t R = 4;  // run r's packed bytes [4, end) land at R (== 4 mod 8)
+    std::vector<uint64_t> ro(run_units), ro2(o.bytes2 ? run_units : 0), po(packs ? run_units + 1 : 0);
+    uint64_t R = 4, R2 = 4;  // run r's packed bytes [4, end) land at R (== 4 mod 8); R2: the second output's
     auto run = [&](int a, int m) -> int {
         // the run's bytes [p0, p1) upload to the same distance from an 8-B boundary (pairs stay 8-B
         // aligned, packed units 4 mod 8); its offsets are rebased to that copy
@@ -234,6 +246,17 @@ int payload_serial(wc_ctx* c, const uint8_t* bytes, const uint64_t* offsets, con
             (e = hipMemcpyAsync(c->h_offsets.p, ro.data(), sizeof(uint64_t) * m, hipMemcpyHostToDevice, c->stream)) !=
                 hipSuccess)
             return hip_fail(c, e, "payload upload");
+        if (o.bytes2) {  // the second input of the run, by the same rule
+            uint64_t q0, q1;
+            byte_span(o.offsets2, o.end2, a, m, q0, q1);
+            const uint64_t shift2 = o.shift + (q0 & 7);
+            for (int i = 0; i < m; ++i) ro2[i] = o.offsets2[a + i] - q0 + shift2;
+            if ((e = hipMemcpyAsync((uint8_t*)c->h_second.p + shift2, o.bytes2 + q0, q1 - q0, hipMemcpyHostToDevice,
+                                    c->stream)) != hipSuccess ||
+                (e = hipMemcpyAsync(c->h_second_off.p, ro2.data(), sizeof(uint64_t) * m, hipMemcpyHostToDevice,
+                                    c->stream)) != hipSuccess)
+                return hip_fail(c, e, "payload upload");
+        }
         int rc2;
         if ((rc2 = step(a, m, (const uint8_t*)c->h_payload.p, (const uint64_t*)c->h_offsets.p, shift + (p1 - p0))))
             return rc2;
@@ -241,7 +264,12 @@ int payload_serial(wc_ctx* c, const uint8_t* bytes, const uint64_t* offsets, con
             // the plan the step left is the run's units': its slots are wc_forward's.  ro is rewritten by
             // the next run: the uploads have finished after the tail's synchronize.
             if ((e = pack_run(c, m, (const uint8_t*)c->h_out.p)) != hipSuccess) return hip_fail(c, e, "pack launch");
-            return packed_run_tail(c, a, m, po, o.payload, o.cap, o.out_offsets, o.kept, R);
+            if ((rc2 = packed_run_tail(c, a, m, po, o.payload, o.cap, o.out_offsets, o.kept, R)) || !o.payload2) return rc2;
+            // the second output through the same staging (the first tail has synchronized; its last copy, out of
+            // the staging, is ahead of this packing on the stream)
+            if ((e = pack_run(c, m, (const uint8_t*)c->h_second.p, c->h_second_cnt.p)) != hipSuccess)
+                return hip_fail(c, e, "pack launch");
+            return packed_run_tail(c, a, m, po, o.payload2, o.cap2, o.out_offsets2, o.kept2, R2, c->h_second_cnt.p);
         }
         if (o.checked) {  // a unit the device refused after all fails the call before this run's cells cross back
             if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return hip_fail(c, e, "packed decode");
@@ -255,6 +283,7 @@ int payload_serial(wc_ctx* c, const uint8_t* bytes, const uint64_t* offsets, con
     };
     rc = WC_OK;
     for (int r = 0; r < nr && rc == WC_OK; ++r) rc = run(rb[r], rb[r + 1] - rb[r]);
+    if (rc == WC_OK && o.payload2) o.out_offsets2[n] = R2 - 4;
     return serial_finish(c, rc, n, packs ? o.out_offsets : nullptr, R, o.results);
 }
 

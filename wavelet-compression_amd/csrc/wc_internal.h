@@ -179,6 +179,39 @@ struct ThinLaunch {
     uint32_t* kept;
     uint32_t* err;
 };
+
+// What launch_split (wc_layers.hip) takes: the thinning's launch (its output is the base) and the rest's side.
+struct SplitLaunch {
+    ThinLaunch thin;
+    const uint64_t* rest_off;  // per unit: the rest's slot, prefix of 24 + 8 * N, == 4 (mod 8)
+    uint32_t* s3;              // positions of the rest's pairs
+    uint32_t* restw;           // per unit: rest pairs (zeroed)
+    uint8_t* rest;
+    uint64_t* rest_offsets;
+    uint32_t* rest_pairs;
+};
+
+// What launch_merge (wc_layers.hip) takes, and its kernels by value: side 0 is a, side 1 is b.  The units'
+// descriptors are ThinDesc's (box, header field, N, dt_begin, out_off; cap = N).
+struct MergeLaunch {
+    const ThinDesc* desc;
+    int n;
+    const FTile* tiles;
+    uint32_t ntiles;
+    const uint8_t* pay[2];
+    const uint64_t* off[2];
+    int ordered;
+    uint32_t* ticket[2];            // per side and unit, zeroed
+    unsigned long long* status[2];  // per side: look-back granules per decode tile, zeroed
+    uint32_t* pos[2];               // per side: the positions of its pairs below N
+    uint32_t* live;                 // [2][n]: their counts (zeroed)
+    uint32_t* overlap;              // [n]: nonzero where a and b hold a pair at one position (zeroed)
+    uint8_t* out;
+    uint64_t* out_offsets;
+    uint32_t* pairs;
+    uint32_t* err;
+};
+
 // One unit of the packed-payload transcoders (wc_pack.hip): the box, the unit's
 // slot in the packed buffer (wc_packed_bound's scheme) and its slot in the
 // standard payload buffer (wc_payload_bound's).  Kept on the device while a
@@ -207,6 +240,7 @@ constexpr unsigned long long kKeyNaNFirst = ~0ull;
 // Error bits raised by kernels (ctx->d_err).
 constexpr uint32_t kErrHeader = 1u;      // payload header disagrees with the unit
 constexpr uint32_t kErrNegativeRun = 2u; // a run length < 0 (reference: UB)
+constexpr uint32_t kErrOverlap = 4u;     // wc_merge: both inputs hold a pair at one position
 
 constexpr uint32_t kEpochMask = 0x3fffffffu;  // epoch bits of a look-back granule (wc_device.h GranuleEpoch32)
 

@@ -53,37 +53,13 @@
 // run counts as run 0 (Sat32; kErrNegativeRun), so positions still grow.
 #include "wc_budget.h"
 #include "wc_pairscan.h"
+#include "wc_thinunit.h"
 
 namespace wc {
 
 constexpr int kThinTopBins = kHistBins + WC_LTOL_SHIFT * (WC_MAX_LEVELS - 1);  // the first digit's values at L = 4
 constexpr int kThinBinStride = 4352;                                           // global bins per split unit
 static_assert(kThinBinStride >= kThinTopBins, "a split unit's global bins hold the first digit");
-
-// A unit's payload as every pass sees it, from the header alone.
-struct ThinUnit {
-    const uint32_t* __restrict__ runs;  // the pairs
-    uint32_t n;                         // pairs the header announces
-    uint32_t T;                         // pair tiles that run
-    uint32_t np;                        // pairs with a scratch entry: min(n, T * kFlatTile)
-    bool ok;                            // the header agrees with the unit
-};
-__device__ __forceinline__ ThinUnit thin_open(const ThinDesc& C, const uint8_t* __restrict__ payload, uint64_t off) {
-    ThinUnit U{nullptr, 0u, 0u, 0u, false};
-    if (off & 3u) return U;
-    const uint8_t* ph = payload + off;
-    int32_t nrle;
-    U.ok = header_ok(C.W, C.H, C.D, C.want, ph, nrle);
-    if (!U.ok) return U;
-    U.runs = reinterpret_cast<const uint32_t*>(ph + 20);
-    U.n = (uint32_t)nrle;
-    const uint32_t ptiles = U.n ? (U.n - 1u) / (uint32_t)kFlatTile + 1u : 1u;
-    U.T = C.N ? min(ptiles, (C.N - 1u) / (uint32_t)kFlatTile + 1u) : 0u;
-    U.np = (uint32_t)min((uint64_t)U.n, (uint64_t)U.T * kFlatTile);
-    return U;
-}
-
-using ThinScan = PairScan<Sat32, Granule62, kFlatTile, LoadPairs>;
 
 template <bool kBudget>
 __global__ __launch_bounds__(kThreads) void k_thin_scan(const ThinDesc* __restrict__ desc,
@@ -417,7 +393,9 @@ __global__ __launch_bounds__(kThreads) void k_thin_units(const ThinDesc* __restr
     if (u == n - 1) out_offsets[n] = C.out_off + 20 + 8ull * k;
 }
 
-hipError_t launch_thin(hipStream_t st, const ThinLaunch& a) {
+// The scan and, in the budget form, the select: {key, pos} per pair in s1, T per unit in keyw
+// (wc_layers.hip's split runs these and then its own compaction).
+hipError_t launch_thin_front(hipStream_t st, const ThinLaunch& a) {
     if (a.n <= 0) return hipSuccess;
     hipError_t e = hipSuccess;
     if (a.ntiles) {
@@ -460,6 +438,13 @@ hipError_t launch_thin(hipStream_t st, const ThinLaunch& a) {
             if ((e = hipGetLastError()) != hipSuccess) return e;
         }
     }
+    return hipSuccess;
+}
+
+hipError_t launch_thin(hipStream_t st, const ThinLaunch& a) {
+    if (a.n <= 0) return hipSuccess;
+    hipError_t e = launch_thin_front(st, a);
+    if (e != hipSuccess) return e;
     if (a.ntiles) {
         k_thin_compact<<<a.ntiles, kThreads, 0, st>>>(a.desc, a.tiles, a.payload, a.offsets, a.ticket[1], a.status[1],
                                                     a.s1, a.s2, a.keyw, a.out, a.keptw, a.err, a.ordered);
