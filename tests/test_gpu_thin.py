@@ -11,8 +11,9 @@ One mixed batch (_mixed() below): pair counts around the wave and the pair tile,
 unit of three pair tiles whose whole middle tile a budget drops (the run across
 it carries over two tile boundaries), units whose first and whose last pair are
 dropped, K = 0, K >= the pair count, a tie at T, boxes 16^3 at L = 4, (32, 16, 32) at
-L = 1..3, (33, 17, 31) at L = 1 and (0, 4, 4), and the
-crafted overshoot and surplus units of decode_payloads.  It runs under every
+L = 1..3, (33, 17, 31) at L = 1 and (0, 4, 4), the
+crafted overshoot and surplus units of decode_payloads, and a unit whose thresholds
+are exactly 0.0 over +-0, NaN, +-inf and subnormals.  It runs under every
 look-back option set and with both select paths (WC_OPT_TOL_SOLO_TILES 1 and
 default).  The references are computed once and left unchanged."""
 import numpy as np
@@ -95,6 +96,9 @@ def _mixed():
     assert len(over) >= 4 and len(surplus) >= 4
     for u in over[::max(1, len(over) // 4)][:4] + surplus[::max(1, len(surplus) // 4)][:4]:
         out.append(Unit(u.name, u.dims, u.L, u.runs, u.bits, "rank"))
+    # thresholds of exactly 0.0 over +-0, NaN, +-inf and subnormals (K above the candidates: T = 0): the one
+    # place where "|c| > t" and "a candidate above t" could part.  Last, so the units before it stay as they were.
+    out.append(Unit("t=0", (16, 16, 16), 2, _at(rng, 4096, 300), _values(rng, 300), 0xFFFFFFFF))
     return out
 
 
@@ -223,6 +227,13 @@ def test_the_batch_shows_what_it_claims(wc):
     assert C.want[by["K>pairs"]][0] == C.us[by["K>pairs"]].payload
     for name in ("tie", "tie-L3"):
         assert C.want[by[name]][4] >= 2 and C.want[by[name]][1] < C.K[by[name]]
+    i = by["t=0"]
+    _, _, _, _, _, _, bits = TR.parse(C.us[i].payload)
+    m = bits & np.uint32(0x7FFFFFFF)
+    assert C.want[i][2] == 0 and not C.thresh[i].any()  # T = 0: the threshold form runs it at 0.0 on both levels
+    assert {0, 0x80000000, 0x7F800000, 0xFF800000} <= set(bits.tolist())
+    assert ((m > 0) & (m < 0x00800000)).any() and (m > 0x7F800000).any()  # a subnormal, a NaN
+    assert C.want[i][1] == int(((m >= 1) & (m <= 0x7F800000)).sum()) < C.us[i].pairs  # every candidate, no other pair
     assert {u.dims for u in C.us} >= {(16, 16, 16), BOX4, BOX5, (0, 4, 4)}
     assert {(u.dims, u.L) for u in C.us} >= {((16, 16, 16), 4), (BOX4, 1), (BOX4, 2), (BOX4, 3), (BOX5, 1)}
     tiles = [-(-min(u.pairs, u.N) // TILE) for u in C.us]

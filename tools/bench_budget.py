@@ -163,6 +163,7 @@ def main():
         "steps": args.steps, "warmup": args.warmup, "frac": args.frac, "thresh": args.thresh,
         "ms_median": {k: round(v, 4) for k, v in med.items()},
         "ms_min": {k: round(min(v), 4) for k, v in times.items()},
+        "ms_p10": {k: round(sorted(v)[int(0.1 * (len(v) - 1))], 4) for k, v in times.items()},
         "ms_p90": {k: round(sorted(v)[int(0.9 * (len(v) - 1))], 4) for k, v in times.items()},
         "legs": legs, "stage_ms": stages,
         "budget_minus_leveltol_ms": {f"L{L}": round(med[f"budget_L{L}"] - med[f"leveltol_L{L}"], 4) for L in Ls},

@@ -31,6 +31,9 @@
 //   k_budget_pick<P>    one wave per split unit (a later launch): the walk over
 //                       the unit's global bins, its state {prefix, above, done}
 //                       and, at the end, thresh / key
+// The select's skeleton (bg_solo, bg_pick, bg_passes) is wc_budget.h's, shared with
+// wc_thin.hip: here a key is a staged coefficient's and the first digit's count
+// sums per-level bin sets.
 // The mask pass and the emit are wc_leveltol.hip's and wc_emit.hip's, unchanged.
 // LDS per workgroup as k_ltol_solo: (NL + 1) x 16 KiB.
 #include "wc_budget.h"
@@ -105,7 +108,6 @@ __device__ __forceinline__ uint32_t bg_top_count(const uint32_t* h, int off2, in
     }
     return c;
 }
-__device__ __forceinline__ int bg_top_bins(int L) { return kHistBins + WC_LTOL_SHIFT * (L - 1); }
 
 // Workgroup u owns unit u unless the unit is split (lt[u].slot != kLtSolo).
 template <int NL>
@@ -118,59 +120,24 @@ __global__ __launch_bounds__(kLtThreads) void k_budget_solo(const UnitDev* __res
     const LtUnit T = lt[u];
     if (T.slot != kLtSolo) return;  // uniform
     __shared__ uint32_t h[(NL + 1) * kHistBins];
-    // found, digit, above: in level 1's second bin set, free once lt_fold has summed it into the first
+    // bg_solo's state words: in level 1's second bin set, free once lt_fold has summed it into the first
     // (a word more of LDS than k_ltol_solo's would cost a workgroup per CU at NL = 1 and NL = 4)
     uint32_t* st = h + kHistBins;
     const UnitDev& U = units[u];
     const LtGeom G = lt_geom(U, T);
-    const uint32_t K = max_pairs[u], nt = U.nftiles;
-    const int L = (int)T.levels, ln = (int)threadIdx.x;
-    float* th = thresh + (size_t)u * WC_MAX_LEVELS;
-    uint32_t* ky = key ? key + u : nullptr;
-
-    lt_zero(h, (NL + 1) * kHistBins);
-    bg_bin_top(h, coef, U, G, 0u, nt);
-    lt_fold(h);
-    if (ln < kWave) {
-        uint32_t above = 0u;
-        int d = 0;
-        const bool found = bg_walk([&](int s) { return bg_top_count(h, 2 * kHistBins, L, s); }, bg_top_bins(L), K, ln,
-                                   above, d);
-        if (ln == 0) {
-            st[0] = found ? 1u : 0u;
-            st[1] = (uint32_t)d;
-            st[2] = above;
-        }
-    }
-    __syncthreads();
-    if (!st[0]) {  // uniform: at most K candidates
-        if (ln == 0) bg_write(0u, L, th, ky);
-        return;
-    }
-    const uint32_t s = st[1];
-    lt_zero(h, kBgMidBins);  // (its barrier: st has been read)
-    bg_bin_mid(h, coef, U, G, 0u, nt, s);
-    __syncthreads();
-    if (ln < kWave) {
-        uint32_t above = st[2];
-        int d = 0;
-        (void)bg_walk([&](int i) { return h[i]; }, kBgMidBins, K, ln, above, d);
-        if (ln == 0) {
-            st[1] = (s << 12) | (uint32_t)d;
-            st[2] = above;
-        }
-    }
-    __syncthreads();
-    const uint32_t prefix = st[1];
-    lt_zero(h, kBgLowBins);
-    bg_bin_low(h, coef, U, G, 0u, nt, prefix);
-    __syncthreads();
-    if (ln < kWave) {
-        uint32_t above = st[2];
-        int d = 0;
-        (void)bg_walk([&](int i) { return h[i]; }, kBgLowBins, K, ln, above, d);
-        if (ln == 0) bg_write((prefix << 7) | (uint32_t)d, L, th, ky);
-    }
+    const uint32_t nt = U.nftiles;
+    const int L = (int)T.levels;
+    bg_solo(
+        h, st, L, max_pairs[u],
+        [&] {
+            lt_zero(h, (NL + 1) * kHistBins);
+            bg_bin_top(h, coef, U, G, 0u, nt);
+            lt_fold(h);
+        },
+        [&](int s) { return bg_top_count(h, 2 * kHistBins, L, s); },
+        [&](uint32_t s) { bg_bin_mid(h, coef, U, G, 0u, nt, s); },
+        [&](uint32_t prefix) { bg_bin_low(h, coef, U, G, 0u, nt, prefix); },
+        [&](uint32_t Tk) { bg_write(Tk, L, thresh + (size_t)u * WC_MAX_LEVELS, key ? key + u : nullptr); });
 }
 
 // Work item i: tiles [items[i].y, + chunk) of split unit items[i].x, digit 1's
@@ -236,32 +203,11 @@ __global__ __launch_bounds__(kWave) void k_budget_pick(const LtUnit* __restrict_
                                                      BudgetState* __restrict__ state, float* __restrict__ thresh,
                                                      uint32_t* __restrict__ key) {
     const uint32_t u = split_units[blockIdx.x];
-    const int L = (int)lt[u].levels, ln = (int)threadIdx.x;
-    const uint32_t K = max_pairs[u];
-    float* th = thresh + (size_t)u * WC_MAX_LEVELS;
-    uint32_t* ky = key ? key + u : nullptr;
-    BudgetState S = state[blockIdx.x];
-    int d = 0;
-    if (P == 1) {
-        const uint32_t* h = gbins + (size_t)blockIdx.x * nl * kHistBins;
-        uint32_t above = 0u;
-        const bool found = bg_walk([&](int s) { return bg_top_count(h, kHistBins, L, s); }, bg_top_bins(L), K, ln, above, d);
-        if (ln == 0) {
-            state[blockIdx.x] = {(uint32_t)d, above, found ? 0u : 1u, 0u};
-            if (!found) bg_write(0u, L, th, ky);
-        }
-        return;
-    }
-    if (S.done) return;  // uniform
-    const uint32_t* h = gbins + (size_t)blockIdx.x * kHistBins;
-    (void)bg_walk([&](int i) { return h[i]; }, P == 2 ? kBgMidBins : kBgLowBins, K, ln, S.above, d);
-    if (ln != 0) return;
-    if (P == 2) {
-        state[blockIdx.x] = {(S.prefix << 12) | (uint32_t)d, S.above, 0u, 0u};
-    } else {
-        state[blockIdx.x] = {S.prefix, S.above, 1u, 0u};
-        bg_write((S.prefix << 7) | (uint32_t)d, L, th, ky);
-    }
+    const int L = (int)lt[u].levels;
+    const uint32_t* h = gbins + (size_t)blockIdx.x * (P == 1 ? nl : 1) * kHistBins;
+    bg_pick<P>(
+        state + blockIdx.x, L, max_pairs[u], [&](int s) { return bg_top_count(h, kHistBins, L, s); }, h,
+        [&](uint32_t T) { bg_write(T, L, thresh + (size_t)u * WC_MAX_LEVELS, key ? key + u : nullptr); });
 }
 
 // lt[n]: the units' descriptors (tol unused); max_pairs[n]; items[nitems]: the
@@ -295,16 +241,15 @@ hipError_t launch_budget(hipStream_t st, const UnitDev* units, int n, const LtUn
     if ((e = hipGetLastError()) != hipSuccess) return e;
     k_budget_pick<1><<<nsplit, kWave, 0, st>>>(lt, split_units, max_pairs, gbins, maxl, state, thresh, key);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(gbins, 0, set_bytes, st)) != hipSuccess) return e;
-    k_budget_digit<2><<<nitems, kLtThreads, 0, st>>>(units, lt, items, chunk, coef, state, gbins);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    k_budget_pick<2><<<nsplit, kWave, 0, st>>>(lt, split_units, max_pairs, gbins, maxl, state, thresh, key);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(gbins, 0, set_bytes, st)) != hipSuccess) return e;
-    k_budget_digit<3><<<nitems, kLtThreads, 0, st>>>(units, lt, items, chunk, coef, state, gbins);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    k_budget_pick<3><<<nsplit, kWave, 0, st>>>(lt, split_units, max_pairs, gbins, maxl, state, thresh, key);
-    return hipGetLastError();
+    return bg_passes<2>(
+        st, gbins, set_bytes,
+        [&](auto P) {
+            k_budget_digit<decltype(P)::value><<<nitems, kLtThreads, 0, st>>>(units, lt, items, chunk, coef, state, gbins);
+        },
+        [&](auto P) {
+            k_budget_pick<decltype(P)::value><<<nsplit, kWave, 0, st>>>(lt, split_units, max_pairs, gbins, maxl, state,
+                                                                       thresh, key);
+        });
 }
 
 }  // namespace wc

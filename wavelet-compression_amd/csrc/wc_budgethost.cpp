@@ -45,10 +45,7 @@ extern "C" int wc_forward_levels_budget_host(wc_ctx* c, const void* cells, int d
     if (n == 0) return WC_OK;
     if (!cells || !payload || !offsets || !kept || !max_pairs) return fail(c, WC_ERR_INVALID, "null buffer");
     std::vector<int32_t> ones;
-    if (!levels) {
-        ones.assign(n, 1);
-        levels = ones.data();
-    }
+    levels = levels_or_ones(levels, n, ones);
     if ((rc = validate_budget(c, units, n, levels))) return rc;
     if (cap < wc_payload_bound(units, n)) return fail(c, WC_ERR_INVALID, "payload_capacity < wc_payload_bound");
     if ((rc = set_device(c))) return rc;

@@ -42,6 +42,24 @@ using namespace wc;
 
 namespace {
 
+// While one lives, get_plan builds dense plans (WC_OPT_INVERSE_ROWS = 0: every unit's pair tiles in
+// dtiles).  The plan's key holds the option, so such a plan is cached beside the batch's default one.
+struct DensePlans {
+    wc_ctx* c;
+    bool rows;
+    explicit DensePlans(wc_ctx* c_) : c(c_), rows(c_->opt_inv_rows) { c->opt_inv_rows = false; }
+    ~DensePlans() { c->opt_inv_rows = rows; }
+};
+// The dense plan of these units; strip_offsets: without their cell offsets (the passes over payloads
+// ignore them, so the key carries none).
+int dense_plan(wc_ctx* c, const wc_unit* units, int n, bool strip_offsets) {
+    DensePlans dense(c);
+    if (!strip_offsets) return get_plan(c, units, n);
+    std::vector<wc_unit> full(units, units + n);
+    for (wc_unit& u : full) u.cell_offset = 0;
+    return get_plan(c, full.data(), n);
+}
+
 // Staged forward, first half: K1 transform into the flat coefficient
 // scratch + per-unit max keys (zeroed state).
 int stage_transform(wc_ctx* c, const void* d_cells, int dtype, double keep, bool sparse) {
@@ -82,7 +100,7 @@ int stage_emit(wc_ctx* c, int n, double keep, const float* gthresh, uint8_t* d_p
     p.units = (const UnitDev*)P.d_units.p;
     p.edesc = (const EmitDesc*)P.d_edesc.p;
     p.n = n;
-    p.ordered = use_ordered(c) ? (c->opt_reverse ? 2u : 1u) : 0u;
+    p.ordered = (uint32_t)tile_order(c);
     p.key = (const unsigned long long*)(st + 16);
     p.tickets = (uint32_t*)(st + 16 + 8ull * n);
     p.status = (unsigned long long*)(st + round_up(16 + 20ull * n, 8));
@@ -850,8 +868,7 @@ struct DecodeState {
 };
 hipError_t decode_state(wc_ctx* c, int n, size_t bytes, bool dense, DecodeState* s) {
     uint8_t* st = (uint8_t*)c->state.p;
-    *s = {(uint32_t*)st, (unsigned long long*)(st + round_up(4ull * n, 8)),
-          use_ordered(c) ? (c->opt_reverse ? 2 : 1) : 0};
+    *s = {(uint32_t*)st, (unsigned long long*)(st + round_up(4ull * n, 8)), tile_order(c)};
     return dense || !s->ordered ? hipMemsetAsync(st, 0, bytes, c->stream) : hipSuccess;
 }
 
@@ -1004,26 +1021,23 @@ int inverse_compact(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offse
         any_direct |= d.direct != 0;
         any_run |= d.direct == 0;
     }
-    // the full units' plan: the decoder ignores their cell offsets, so the key carries none
-    std::vector<wc_unit> full(units, units + n);
-    for (wc_unit& u : full) u.cell_offset = 0;
-    const bool rows = c->opt_inv_rows;
-    c->opt_inv_rows = false;  // the plans' key holds it (wc_inverse_levels)
     const FTile* dtiles = nullptr;
     uint32_t ndt = 0;
     size_t dstate = 0;
-    if ((rc = get_plan(c, full.data(), n)) == WC_OK) {
-        const Plan& F = c->plan;
-        dtiles = (const FTile*)F.d_dtiles.p;  // the plan moves into the cache below: its buffers stay
-        dstate = decode_state_bytes(F);
-        // dtiles is ordered by tile index, then unit: the tiles below maxt are a prefix of it
-        for (int u = 0; u < n; ++u) {
-            desc[u].dt_begin = F.units[u].dt_begin;
-            ndt += std::min(F.units[u].ndt, maxt);
+    {
+        DensePlans dense(c);  // both plans, as wc_inverse_levels': the full units' (the decode's tiles), then the compact units'
+        if ((rc = dense_plan(c, units, n, true)) == WC_OK) {
+            const Plan& F = c->plan;
+            dtiles = (const FTile*)F.d_dtiles.p;  // the plan moves into the cache below: its buffers stay
+            dstate = decode_state_bytes(F);
+            // dtiles is ordered by tile index, then unit: the tiles below maxt are a prefix of it
+            for (int u = 0; u < n; ++u) {
+                desc[u].dt_begin = F.units[u].dt_begin;
+                ndt += std::min(F.units[u].ndt, maxt);
+            }
+            rc = get_plan(c, out_units, n);
         }
-        rc = get_plan(c, out_units, n);
     }
-    c->opt_inv_rows = rows;
     if (rc || (rc = ensure_scratch(c)) || (rc = ensure(c, c->state, dstate))) return rc;
     const Plan& P = c->plan;
     for (int u = 0; u < n; ++u) desc[u].dst_off = P.units[u].coef_off;
@@ -1183,10 +1197,7 @@ int wc_forward_levels_budget(wc_ctx* c, const void* d_cells, int dtype, const wc
     int rc = forward_levels_begin(
         c, d_cells, dtype, units, n, d_payload, cap, d_offsets, d_kept, max_pairs != nullptr,
         [&] {
-            if (!levels) {
-                ones.assign(n, 1);
-                levels = ones.data();
-            }
+            levels = levels_or_ones(levels, n, ones);
             return validate_budget(c, units, n, levels);
         },
         {{d_thresh, "thresh", 4}, {d_key, "key", 4}}, &run);
@@ -1285,11 +1296,7 @@ int inverse_dense(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets
         (rc = check_aligned(c, d_offsets, "offsets", 8)) || (rc = check_aligned(c, d_out, "out")))
         return rc;
     if ((rc = set_device(c))) return rc;
-    const bool rows = c->opt_inv_rows;
-    c->opt_inv_rows = false;  // the plan's key holds it: this batch's dense plan is cached beside the default one
-    rc = get_plan(c, units, n);
-    c->opt_inv_rows = rows;
-    if (rc || (rc = ensure_scratch(c))) return rc;
+    if ((rc = dense_plan(c, units, n, false)) || (rc = ensure_scratch(c))) return rc;
     LevelWork w;
     if ((rc = upload_levels(c, n, levels, &w))) return rc;
     const Plan& P = c->plan;
@@ -1329,10 +1336,7 @@ int inverse_coarse(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offset
     if (!d_payload || !d_offsets || !reduce || !out_units || !d_out) return fail(c, WC_ERR_INVALID, "null buffer");
     if (packed_cap && (rc = validate_pack(c, units, n))) return rc;
     std::vector<int32_t> ones;
-    if (!levels) {
-        ones.assign(n, 1);
-        levels = ones.data();
-    }
+    levels = levels_or_ones(levels, n, ones);
     if ((rc = validate_levels(c, units, n, levels)) || (rc = validate_coarse(c, units, n, levels, reduce, out_units)))
         return rc;
     if (std::all_of(reduce, reduce + n, [](int32_t r) { return r == 0; }))
@@ -1360,10 +1364,7 @@ int inverse_region(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offset
     if (!d_payload || !d_offsets || !regions || !out_units || !d_out) return fail(c, WC_ERR_INVALID, "null buffer");
     if (packed_cap && (rc = validate_pack(c, units, n))) return rc;
     std::vector<int32_t> ones, zeros;
-    if (!levels) {
-        ones.assign(n, 1);
-        levels = ones.data();
-    }
+    levels = levels_or_ones(levels, n, ones);
     if (!reduce) {
         zeros.assign(n, 0);
         reduce = zeros.data();
@@ -1410,13 +1411,28 @@ int wc_inverse_region(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_off
 
 namespace wc {
 
+// What every pass over a unit's pairs needs of it (wc_thin.hip, wc_layers.hip): the box, the header's
+// ncoeff field, N and L; its select is one workgroup's until the caller splits it.
+static ThinDesc thin_desc(const wc_unit& f, int L) {
+    const uint64_t N = (uint64_t)f.nx * f.ny * f.nz;
+    ThinDesc d{};
+    d.W = f.nx;
+    d.H = f.ny;
+    d.D = f.nz;
+    d.want = L >= 2 ? -L : (int32_t)N;
+    d.N = (uint32_t)N;
+    d.L = (uint32_t)L;
+    d.slot = kLtSolo;
+    return d;
+}
+
 // Thinning in the compressed domain (wc_thin.hip).  The plan of the units (dense,
 // without cell offsets: the one wc_inverse_region's decode uses) gives the pair
 // tiles and their look-back granules; the call's descriptors and split layout go
 // through the pinned block.  Everything of wc_ctx::thin is sized and grown here,
 // before the first launch; the state words are cleared on the stream.
-// With `so` the call is a split (wc_layers.hip): the same descriptors, plan and scratch, the rest's slots
-// (wc_forward's layout), 4 B per coefficient more for the rest's positions, and launch_split.
+// With `so` the call is a split: the same descriptors, plan, scratch and launch, with the rest's slots
+// (wc_forward's layout), its count words and 4 B per coefficient more for the rest's positions.
 static int thin_or_split(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
                          const int32_t* levels, const uint32_t* max_pairs, const float* thresh, bool full_slots,
                          uint8_t* d_out, uint64_t out_capacity, uint64_t* d_out_offsets, uint32_t* d_kept,
@@ -1425,27 +1441,19 @@ static int thin_or_split(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_
     int rc;
     if ((rc = validate_levels(c, units, n, levels))) return rc;
     std::vector<ThinDesc> desc(n);
-    std::vector<uint64_t> rest_off(so ? n : 0);
     uint64_t cursor = 4, rcursor = 4;
     for (int u = 0; u < n; ++u) {
         const wc_unit& f = units[u];
-        const uint64_t N = (uint64_t)f.nx * f.ny * f.nz;
         const int L = levels[u];
+        ThinDesc& d = desc[u];
+        d = thin_desc(f, L);
+        const uint64_t N = d.N;
         if (so) {
-            rest_off[u] = rcursor;
+            d.rest_off = rcursor;
             rcursor += 24 + 8 * N;
         }
-        ThinDesc& d = desc[u];
-        d = ThinDesc{};
         d.dmagic = N ? rows_magic(f.nz) : 0;
         d.hmagic = N ? rows_magic(f.ny) : 0;
-        d.W = f.nx;
-        d.H = f.ny;
-        d.D = f.nz;
-        d.want = L >= 2 ? -L : (int32_t)N;
-        d.N = (uint32_t)N;
-        d.L = (uint32_t)L;
-        d.slot = kLtSolo;
         d.K = budget ? max_pairs[u] : 0u;
         d.cap = budget && !full_slots ? (uint32_t)std::min<uint64_t>(d.K, N) : (uint32_t)N;
         for (int l = 0; l < L && !budget; ++l) {
@@ -1478,13 +1486,7 @@ static int thin_or_split(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_
         (rc = check_aligned(c, d_key, "key", 4)))
         return rc;
     if ((rc = set_device(c))) return rc;
-    std::vector<wc_unit> full(units, units + n);
-    for (wc_unit& u : full) u.cell_offset = 0;
-    const bool rows = c->opt_inv_rows;
-    c->opt_inv_rows = false;  // a dense plan: every unit's pair tiles in dtiles
-    rc = get_plan(c, full.data(), n);
-    c->opt_inv_rows = rows;
-    if (rc) return rc;
+    if ((rc = dense_plan(c, units, n, true))) return rc;  // every unit's pair tiles in dtiles
     const Plan& P = c->plan;
     // as build_leveltol: a unit of more than opt_tol_solo tiles is split into runs of `chunk` tiles
     const uint32_t solo = (uint32_t)c->opt_tol_solo, chunk = std::min<uint32_t>(solo, 8);
@@ -1501,9 +1503,9 @@ static int thin_or_split(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_
         for (uint32_t t = 0; t < d.ndt; t += chunk) items.push_back(make_uint2((uint32_t)u, t));
     }
     const size_t nsplit = split.size(), nitems = items.size();
-    // the pinned blob: ThinDesc[n] | items[nitems] | split_units[nsplit] | (a split) rest_off[n]
+    // the pinned blob: ThinDesc[n] | items[nitems] | split_units[nsplit]
     const size_t o_items = sizeof(ThinDesc) * n, o_split = o_items + sizeof(uint2) * nitems,
-                 o_rest = round_up(o_split + 4 * nsplit, 8), in_bytes = so ? o_rest + 8ull * n : o_split + 4 * nsplit;
+                 in_bytes = o_split + 4 * nsplit;
     // wc_ctx::thin: [ticket[2][n] | keptw[n] | keyw[n] | (a split) restw[n] | status[2][tiles]] (cleared) |
     //               state[nsplit] | thresh[n][4] | gbins[nsplit][4352] | s2[tiles * kFlatTile] |
     //               s1[tiles * kFlatTile] | (a split) s3[tiles * kFlatTile]
@@ -1517,7 +1519,6 @@ static int thin_or_split(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_
     std::memcpy(pin, desc.data(), sizeof(ThinDesc) * n);
     if (nitems) std::memcpy(pin + o_items, items.data(), sizeof(uint2) * nitems);
     if (nsplit) std::memcpy(pin + o_split, split.data(), 4 * nsplit);
-    if (so) std::memcpy(pin + o_rest, rest_off.data(), 8ull * n);
     if ((rc = pin_upload(c, in_bytes))) return rc;
     uint8_t* s = (uint8_t*)c->thin.p;
     const uint8_t* blob = (const uint8_t*)c->tol_in.p;
@@ -1531,7 +1532,7 @@ static int thin_or_split(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_
     a.payload = d_payload;
     a.offsets = d_offsets;
     a.budget = budget;
-    a.ordered = use_ordered(c) ? (c->opt_reverse ? 2 : 1) : 0;
+    a.ordered = tile_order(c);
     a.ticket[0] = (uint32_t*)s;
     a.ticket[1] = (uint32_t*)s + n;
     a.keptw = (uint32_t*)s + 2 * (size_t)n;
@@ -1553,20 +1554,15 @@ static int thin_or_split(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_
     a.out_offsets = d_out_offsets;
     a.kept = d_kept;
     a.err = (uint32_t*)c->errflag.p;
-    StageTimer t(c, WC_STAGE_TOL);
     if (so) {
-        SplitLaunch b{};
-        b.thin = a;
-        b.rest_off = (const uint64_t*)(blob + o_rest);
-        b.s3 = (uint32_t*)(s + o_s3);
-        b.restw = (uint32_t*)s + 4 * (size_t)n;
-        b.rest = so->d_rest;
-        b.rest_offsets = so->d_offsets;
-        b.rest_pairs = so->d_pairs;
-        if ((e = launch_split(c->stream, b)) != hipSuccess) return hip_fail(c, e, "split launch");
-    } else if ((e = launch_thin(c->stream, a)) != hipSuccess) {
-        return hip_fail(c, e, "thin launch");
+        a.rest = so->d_rest;
+        a.rest_offsets = so->d_offsets;
+        a.rest_pairs = so->d_pairs;
+        a.s3 = (uint32_t*)(s + o_s3);
+        a.restw = (uint32_t*)s + 4 * (size_t)n;
     }
+    StageTimer t(c, WC_STAGE_TOL);
+    if ((e = launch_thin(c->stream, a)) != hipSuccess) return hip_fail(c, e, so ? "split launch" : "thin launch");
     c->err_check_pending = true;  // malformed payloads surface at the next wc_synchronize
     return WC_OK;
 }
@@ -1596,20 +1592,11 @@ int merge_device(wc_ctx* c, const uint8_t* d_a, const uint64_t* d_a_offsets, con
     std::vector<ThinDesc> desc(n);
     uint64_t cursor = 4;
     for (int u = 0; u < n; ++u) {
-        const wc_unit& f = units[u];
-        const uint64_t N = (uint64_t)f.nx * f.ny * f.nz;
         ThinDesc& d = desc[u];
-        d = ThinDesc{};
-        d.W = f.nx;
-        d.H = f.ny;
-        d.D = f.nz;
-        d.want = levels[u] >= 2 ? -levels[u] : (int32_t)N;
-        d.N = (uint32_t)N;
-        d.L = (uint32_t)levels[u];
-        d.slot = kLtSolo;
-        d.cap = (uint32_t)N;
+        d = thin_desc(units[u], levels[u]);
+        d.cap = d.N;
         d.out_off = cursor;
-        cursor += 24 + 8 * N;
+        cursor += 24 + 8ull * d.N;
     }
     if (out_capacity < cursor) return fail(c, WC_ERR_INVALID, "out_capacity < wc_merge_bound");
     for (const uint8_t* in : {d_a, d_b}) {  // an input's length is not known here: its start inside the output's extent
@@ -1622,13 +1609,7 @@ int merge_device(wc_ctx* c, const uint8_t* d_a, const uint64_t* d_a_offsets, con
         (rc = check_aligned(c, d_pairs, "pairs", 4)))
         return rc;
     if ((rc = set_device(c))) return rc;
-    std::vector<wc_unit> full(units, units + n);
-    for (wc_unit& u : full) u.cell_offset = 0;
-    const bool rows = c->opt_inv_rows;
-    c->opt_inv_rows = false;  // a dense plan: every unit's pair tiles in dtiles
-    rc = get_plan(c, full.data(), n);
-    c->opt_inv_rows = rows;
-    if (rc) return rc;
+    if ((rc = dense_plan(c, units, n, true))) return rc;  // every unit's pair tiles in dtiles
     const Plan& P = c->plan;
     uint64_t tiles = 0;
     for (int u = 0; u < n; ++u) {
@@ -1654,7 +1635,7 @@ int merge_device(wc_ctx* c, const uint8_t* d_a, const uint64_t* d_a_offsets, con
     a.pay[1] = d_b;
     a.off[0] = d_a_offsets;
     a.off[1] = d_b_offsets;
-    a.ordered = use_ordered(c) ? (c->opt_reverse ? 2 : 1) : 0;
+    a.ordered = tile_order(c);
     a.ticket[0] = (uint32_t*)s;
     a.ticket[1] = (uint32_t*)s + n;
     a.live = (uint32_t*)s + 2 * (size_t)n;
@@ -1699,7 +1680,7 @@ int wc_thin_budget(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offset
                        d_out_offsets, d_kept, d_thresh, d_key);
 }
 
-// Progressive layers (wc_layers.hip): a payload into (base, rest), and two payloads into their union.
+// Progressive layers (wc_thin.hip's split, wc_layers.hip's merge): a payload into (base, rest), and two payloads into their union.
 int wc_split_budget(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
                     const int32_t* levels, const uint32_t* max_pairs, uint8_t* d_base, uint64_t base_capacity,
                     uint64_t* d_base_offsets, uint32_t* d_kept, uint8_t* d_rest, uint64_t rest_capacity,
@@ -1771,10 +1752,7 @@ int wc_inverse_packed(wc_ctx* c, const uint8_t* d_packed, const uint64_t* d_pack
     if (!d_packed || !d_packed_offsets || !d_out) return fail(c, WC_ERR_INVALID, "null buffer");
     if ((rc = validate_pack(c, units, n))) return rc;
     std::vector<int32_t> ones;
-    if (!levels) {
-        ones.assign(n, 1);
-        levels = ones.data();
-    }
+    levels = levels_or_ones(levels, n, ones);
     if ((rc = validate_levels(c, units, n, levels))) return rc;
     return inverse_dense(c, d_packed, d_packed_offsets, units, n, levels, d_out, &packed_capacity);
 }

@@ -146,12 +146,10 @@ hipError_t launch_unpack_units(hipStream_t, const PackDesc*, const FTile* tiles,
                                const uint64_t* packed_offsets, uint64_t cap, int n, uint8_t* payload, uint64_t* offsets,
                                uint32_t* kept, uint32_t* err);
 
-// wc_thin.hip: the passes of wc_thin_budget / wc_thin_thresh (wc_internal.h ThinLaunch)
+// wc_thin.hip: the passes of wc_thin_budget / wc_thin_thresh and, with the rest's side set, of
+// wc_split_budget / wc_split_thresh (wc_internal.h ThinLaunch)
 hipError_t launch_thin(hipStream_t, const ThinLaunch&);
-// its scan and select alone (the front of wc_split_budget)
-hipError_t launch_thin_front(hipStream_t, const ThinLaunch&);
-// wc_layers.hip: the passes of wc_split_budget / wc_split_thresh and of wc_merge
-hipError_t launch_split(hipStream_t, const SplitLaunch&);
+// wc_layers.hip: the passes of wc_merge
 hipError_t launch_merge(hipStream_t, const MergeLaunch&);
 
 struct DevBuf {
@@ -282,7 +280,7 @@ struct wc_ctx {
     int pk_vbytes = 0;
     uint32_t pk_ntiles = 0;
     wc::DevBuf pk_in, pk_out, pk_off, pk_bytes;
-    // wc_thin_budget / wc_thin_thresh: per-call state, select bins and the two pair scratches (wc_thin.hip)
+    // wc_thin_budget / wc_thin_thresh / wc_split_*: per-call state, select bins and the pair scratches (wc_thin.hip)
     wc::DevBuf thin;
     // wc_merge: per-call state and the two position rows (wc_layers.hip).  payload_serial's second stream:
     // a split's rest slots with their offsets and counts, or a merge's second input with its offsets
@@ -321,6 +319,14 @@ hipEvent_t take_event(wc_ctx* c);
 int upload(wc_ctx* c, DevBuf& d, const void* h, size_t bytes, const char* what);
 int set_device(wc_ctx* c);
 bool use_ordered(const wc_ctx* c);
+// the look-back kernels' tile-order argument: 0 tickets, 1 plan order, 2 reversed (WC_OPT_REVERSE_TILES)
+inline int tile_order(const wc_ctx* c) { return use_ordered(c) ? (c->opt_reverse ? 2 : 1) : 0; }
+// levels, or n ones in `storage` where the caller gave none (every unit L = 1)
+inline const int32_t* levels_or_ones(const int32_t* levels, int n, std::vector<int32_t>& storage) {
+    if (levels) return levels;
+    storage.assign(n, 1);
+    return storage.data();
+}
 int check_kernel_errors(wc_ctx* c);
 uint64_t cells_extent(const wc_unit* units, int n);
 

@@ -131,12 +131,13 @@ struct BudgetState {
 };
 static_assert(sizeof(BudgetState) == 16, "one 16-B load");
 
-// One unit of the compressed-domain thinning (wc_thin.hip).  Built per call: the
-// levels, the budget or thresholds and the output slot are not part of a plan.
+// One unit of the pair selection (wc_thin.hip: thinning and split).  Built per call: the
+// levels, the budget or thresholds and the output slots are not part of a plan.
 struct ThinDesc {
     uint64_t dmagic;     // div_rows magic of D: row = floor(position / D)
     uint64_t hmagic;     // div_rows magic of H: I = floor(row / H)
     uint64_t out_off;    // the unit's output slot: prefix of 24 + 8 * cap, == 4 (mod 8)
+    uint64_t rest_off;   // a split: the rest's slot, prefix of 24 + 8 * N, == 4 (mod 8); else 0
     int32_t W, H, D;     // the box
     int32_t want;        // the header's ncoeff field: W*H*D, or -L for L >= 2
     uint32_t N;          // W*H*D
@@ -147,10 +148,12 @@ struct ThinDesc {
     uint32_t cap;        // pairs the slot holds: min(K, N), or N
     float th[4];         // threshold form: t_1..t_L
 };
-static_assert(sizeof(ThinDesc) == 80, "descriptor of 8-B members first");
+static_assert(sizeof(ThinDesc) == 88, "descriptor of 8-B members first");
 
-// What launch_thin (wc_thin.hip) takes: the passes of wc_thin_budget / wc_thin_thresh over the plan's
-// decode tiles of the units (budget: the radix select between the scan and the compaction).
+// What launch_thin (wc_thin.hip) takes: the passes of wc_thin_budget / wc_thin_thresh and of
+// wc_split_budget / wc_split_thresh over the plan's decode tiles of the units (budget: the radix
+// select between the key pass and the compaction).  The kept pairs are the output (a split's base);
+// a split also gives the rest's side, which a thin call leaves null.
 struct ThinLaunch {
     const ThinDesc* desc;
     int n;
@@ -160,11 +163,11 @@ struct ThinLaunch {
     const uint64_t* offsets;
     bool budget;
     int ordered;
-    uint32_t* ticket[2];            // scan, compaction: per unit, zeroed
+    uint32_t* ticket[2];            // key pass, compaction: per unit, zeroed
     unsigned long long* status[2];  // their look-back granules, per decode tile, zeroed
     uint2* s1;                      // {key, pos} per pair
     uint32_t* s2;                   // positions of the kept pairs
-    uint32_t* keyw;                 // per unit: T (zeroed: the threshold form's)
+    uint32_t* keyw;                 // per unit: T (budget)
     uint32_t* keptw;                // per unit: kept pairs (zeroed)
     float* thresh;                  // n x WC_MAX_LEVELS (budget)
     uint32_t* key_out;              // the caller's d_key or null
@@ -178,17 +181,11 @@ struct ThinLaunch {
     uint64_t* out_offsets;
     uint32_t* kept;
     uint32_t* err;
-};
-
-// What launch_split (wc_layers.hip) takes: the thinning's launch (its output is the base) and the rest's side.
-struct SplitLaunch {
-    ThinLaunch thin;
-    const uint64_t* rest_off;  // per unit: the rest's slot, prefix of 24 + 8 * N, == 4 (mod 8)
-    uint32_t* s3;              // positions of the rest's pairs
-    uint32_t* restw;           // per unit: rest pairs (zeroed)
-    uint8_t* rest;
+    uint8_t* rest;                  // a split: the rest's buffer, else null (and so the four below)
     uint64_t* rest_offsets;
     uint32_t* rest_pairs;
+    uint32_t* s3;                   // positions of the rest's pairs
+    uint32_t* restw;                // per unit: rest pairs (zeroed)
 };
 
 // What launch_merge (wc_layers.hip) takes, and its kernels by value: side 0 is a, side 1 is b.  The units'

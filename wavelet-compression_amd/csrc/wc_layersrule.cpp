@@ -1,6 +1,6 @@
 // wc_layersrule.cpp — the rule of the progressive layers on one standard payload
 // (wc_split_unit and wc_merge_unit in include/wavelet_amd.h): the host restatement
-// of wc_layers.hip.  A split is a thinning (wc_thinrule.cpp's wc_thin_unit, called
+// of wc_thin.hip's split and wc_layers.hip's merge.  A split is a thinning (wc_thinrule.cpp's wc_thin_unit, called
 // as it stands) and its complement inside the canonical form; a merge is the union
 // of two position-sorted pair lists.  Both write the reference's run rule on what
 // they keep.
