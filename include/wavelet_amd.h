@@ -607,6 +607,79 @@ int wc_thin_thresh_host(wc_ctx* ctx, const uint8_t* payload, const uint64_t* off
                         const int32_t* levels, const float* thresh, uint8_t* out, uint64_t out_capacity,
                         uint64_t* out_offsets, uint32_t* kept);
 
+/* Thinning and splitting to an RMSE tolerance in the compressed domain (not in the
+ * reference): the third selection rule of the thinning above.  The caller states
+ * an error per unit, as for wc_forward_levels_tol, and the rule of that mode runs
+ * on the payload's pairs: no cell and no dense coefficient exists.
+ *
+ * The rule.  P, W x H x D, L, N and A(P) as in the thinning rule above; lvl and
+ * the selection rule as in wc_forward_levels_tol's section.
+ *   thin_tol(P, tol):
+ *   1. cnt[l][b] = the counts wc_forward_levels_tol's rule takes on A(P), from the
+ *      pairs alone: a pair below N at level l with magnitude bits m <= 0x7F800000
+ *      counts in bin m >> WC_HIST_SHIFT; a NaN pair below N counts nowhere; bin 0
+ *      of level l additionally gets N_l - (pairs of level l below N, NaN
+ *      included), the exact zeros of A(P); N_l = the positions of level l =
+ *      prod(dims >> (l-1)) - prod(dims >> l) for l < L, prod(dims >> (L-1)) for
+ *      l = L.
+ *   2. (thresh_1..L, bound) = wc_tol_levels_threshold(cnt, L, N, tol), operation
+ *      for operation.
+ *   3. The output is thin_thresh(P, thresh_1..L).
+ *   split_tol(P, tol) = (base, rest): base = thin_tol(P, tol), rest = its
+ *   complement in canon(P), exactly as in split_thresh (canon, split and merge:
+ *   the progressive layers' section below).
+ * Units: those wc_forward_levels_tol accepts (even dimensions at L = 1, 2^L
+ * dividing the box otherwise); a unit without cells keeps nothing, bound 0.
+ * Consequences: on a NaN-free payload that holds every candidate (a thresh = 0.0f
+ * payload), thin_tol(P, tol) is byte for byte wc_forward_levels_tol at tol,
+ * thresholds and bound included (a NaN coefficient is "not counted" by the forward
+ * but a zero of A(P): NaN-bearing units are outside this equality only);
+ * tol = 0 gives canon(P); tol = +inf drops every finite pair (thresh_l = FLT_MAX:
+ * a +-inf pair stays, as in the forward); merge(split_tol(P, tol)) == canon(P);
+ * bound <= tol; bound is the RMSE this thinning adds for the real-number
+ * transform, and the sets successive thinnings drop are disjoint, so the squares
+ * of their bounds add: a payload written at tol0 and thinned with bound1 is
+ * within sqrt(tol0^2 + bound1^2) of the original.
+ *
+ *   wc_thin_tol_unit / wc_split_tol_unit: host-only, no device; the rule on one
+ *     payload, on wc_thin_unit / wc_split_unit.  thresh_out (levels floats) and
+ *     bound are nullable.  A NaN or negative tol, or a box the mode does not
+ *     accept: WC_ERR_INVALID; otherwise as wc_thin_unit / wc_split_unit.
+ *   wc_thin_tol / wc_split_tol: the arguments of wc_thin_thresh / wc_split_thresh
+ *     with tol (n doubles, HOST, consumed before the call returns) in place of
+ *     thresh, and d_thresh (n x WC_MAX_LEVELS floats, entries past levels[u]
+ *     written 0.0f) and d_bound (n doubles): device, nullable.  Capacities:
+ *     wc_thin_bound(units, n, NULL) and wc_split_bound(units, n, NULL, ..).
+ *     Asynchronous on the context's stream; nothing is read back between the
+ *     passes; nothing is left staged.  A NaN or negative tolerance, or a unit
+ *     with cells and an odd dimension (an L = 1 unit): WC_ERR_INVALID naming the
+ *     unit, before anything is launched; outputs stay untouched.  A packed unit
+ *     or a header that disagrees with its unit: as in wc_thin_thresh (its slot
+ *     untouched, its counts 0; its d_thresh and d_bound entries are written 0).
+ *     Scratch: the thinning's 12 B (the split's 16 B) per coefficient, and 64 KiB
+ *     of bins per unit of more than WC_OPT_TOL_SOLO_TILES pair tiles.
+ *   wc_thin_tol_host / wc_split_tol_host: host buffers, as wc_thin_thresh_host /
+ *     wc_split_thresh_host; thresh (n x WC_MAX_LEVELS) and bound (n): host,
+ *     nullable. */
+int wc_thin_tol_unit(const uint8_t* payload, size_t len, double tol, uint8_t* out, size_t cap, size_t* written,
+                     float* thresh_out, double* bound);
+int wc_split_tol_unit(const uint8_t* payload, size_t len, double tol, uint8_t* base, size_t base_cap, size_t* base_len,
+                      uint8_t* rest, size_t rest_cap, size_t* rest_len, float* thresh_out, double* bound);
+int wc_thin_tol(wc_ctx* ctx, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                const int32_t* levels, const double* tol, uint8_t* d_out, uint64_t out_capacity,
+                uint64_t* d_out_offsets, uint32_t* d_kept, float* d_thresh, double* d_bound);
+int wc_split_tol(wc_ctx* ctx, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                 const int32_t* levels, const double* tol, uint8_t* d_base, uint64_t base_capacity,
+                 uint64_t* d_base_offsets, uint32_t* d_kept, uint8_t* d_rest, uint64_t rest_capacity,
+                 uint64_t* d_rest_offsets, uint32_t* d_rest_pairs, float* d_thresh, double* d_bound);
+int wc_thin_tol_host(wc_ctx* ctx, const uint8_t* payload, const uint64_t* offsets, const wc_unit* units, int n,
+                     const int32_t* levels, const double* tol, uint8_t* out, uint64_t out_capacity,
+                     uint64_t* out_offsets, uint32_t* kept, float* thresh, double* bound);
+int wc_split_tol_host(wc_ctx* ctx, const uint8_t* payload, const uint64_t* offsets, const wc_unit* units, int n,
+                      const int32_t* levels, const double* tol, uint8_t* base, uint64_t base_capacity,
+                      uint64_t* base_offsets, uint32_t* kept, uint8_t* rest, uint64_t rest_capacity,
+                      uint64_t* rest_offsets, uint32_t* rest_pairs, float* thresh, double* bound);
+
 /* Opt-in progressive layers in the compressed domain (not in the reference): the
  * complement of a thinning, and the union of payloads.  A payload becomes a stack
  * of layers; any prefix of the stack, merged, is a standard payload every decoder

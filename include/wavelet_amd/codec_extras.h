@@ -85,6 +85,16 @@ std::vector<CompressedWavelet> compress_budget(multiBox3D& box, std::vector<int>
 std::vector<CompressedWavelet> thin_budget(const std::vector<CompressedWavelet>& compressed, double ratio);
 std::vector<CompressedWavelet> thin_thresh(const std::vector<CompressedWavelet>& compressed, float thresh);
 
+// Compressed structs thinned to a tolerated RMSE in the compressed domain (GPU,
+// wc_thin_tol_host; not in the reference): compress_rmse's per-level selection on the
+// array each struct decodes to.  `rmse` bounds the error this thinning ADDS (for the
+// real-number transform): a struct made at rmse0 and thinned at rmse1 is within
+// sqrt(rmse0^2 + rmse1^2) of the original component.  A struct that holds every
+// non-zero coefficient (thresh = 0) thinned at `rmse` is byte for byte what
+// compress_rmse gives at `rmse`.  Components with cells need even dimensions (the
+// library's message otherwise); a NaN or negative rmse exits with a message.
+std::vector<CompressedWavelet> thin_rmse(const std::vector<CompressedWavelet>& compressed, double rmse);
+
 // Progressive layers in the compressed domain (GPU, wc_split_budget_host /
 // wc_split_thresh_host / wc_merge_host; not in the reference).  split_*: base[i] is
 // exactly thin_budget's / thin_thresh's struct for compressed[i]; rest[i] holds every
@@ -98,6 +108,7 @@ struct Layers {
 };
 Layers split_budget(const std::vector<CompressedWavelet>& compressed, double ratio);
 Layers split_thresh(const std::vector<CompressedWavelet>& compressed, float thresh);
+Layers split_rmse(const std::vector<CompressedWavelet>& compressed, double rmse);  // base[i] = thin_rmse's struct (wc_split_tol_host)
 std::vector<CompressedWavelet> merge(const std::vector<CompressedWavelet>& a, const std::vector<CompressedWavelet>& b);
 
 // compress() whose files hold packed units (GPU, wc_pack_host after the forward; not

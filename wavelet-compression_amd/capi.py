@@ -44,6 +44,7 @@ EXPORTED = (
     "wc_thin_unit", "wc_thin_bound", "wc_thin_budget", "wc_thin_thresh", "wc_thin_budget_host", "wc_thin_thresh_host",
     "wc_split_unit", "wc_merge_unit", "wc_split_bound", "wc_merge_bound", "wc_split_budget", "wc_split_thresh",
     "wc_merge", "wc_split_budget_host", "wc_split_thresh_host", "wc_merge_host",
+    "wc_thin_tol_unit", "wc_split_tol_unit", "wc_thin_tol", "wc_split_tol", "wc_thin_tol_host", "wc_split_tol_host",
 )
 WC_MAX_LEVELS = 4  # levels of the opt-in multi-level transform (1 = the reference's codec)
 WC_PACK_MAX_CELLS = 1 << 21  # the largest unit wc_pack / wc_unpack take (the host rule has no limit)
@@ -194,6 +195,15 @@ def load_library() -> ctypes.CDLL:
         "wc_thin_thresh": (i32, [vp, vp, vp, up, i32, vp, vp, vp, u64, vp, vp]),
         "wc_thin_budget_host": (i32, [vp, vp, vp, up, i32, vp, vp, vp, u64, vp, vp, vp, vp]),
         "wc_thin_thresh_host": (i32, [vp, vp, vp, up, i32, vp, vp, vp, u64, vp, vp]),
+        "wc_thin_tol_unit": (i32, [vp, ctypes.c_size_t, ctypes.c_double, vp, ctypes.c_size_t,
+                                   ctypes.POINTER(ctypes.c_size_t), vp, ctypes.POINTER(ctypes.c_double)]),
+        "wc_split_tol_unit": (i32, [vp, ctypes.c_size_t, ctypes.c_double, vp, ctypes.c_size_t,
+                                    ctypes.POINTER(ctypes.c_size_t), vp, ctypes.c_size_t,
+                                    ctypes.POINTER(ctypes.c_size_t), vp, ctypes.POINTER(ctypes.c_double)]),
+        "wc_thin_tol": (i32, [vp, vp, vp, up, i32, vp, vp, vp, u64, vp, vp, vp, vp]),
+        "wc_thin_tol_host": (i32, [vp, vp, vp, up, i32, vp, vp, vp, u64, vp, vp, vp, vp]),
+        "wc_split_tol": (i32, [vp, vp, vp, up, i32, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp, vp]),
+        "wc_split_tol_host": (i32, [vp, vp, vp, up, i32, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp, vp]),
         "wc_split_unit": (i32, [vp, ctypes.c_size_t, vp, vp, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
                                 vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint32),
                                 vp]),
@@ -443,6 +453,30 @@ class Context:
         self._check(self._L.wc_thin_thresh(self._h, ctypes.c_void_p(d_payload), ctypes.c_void_p(d_offsets), units, n,
                                            lv.ctypes.data, t.ctypes.data, ctypes.c_void_p(d_out), int(capacity),
                                            ctypes.c_void_p(d_out_offsets), ctypes.c_void_p(d_kept)))
+
+    def thin_tol(self, d_payload: int, d_offsets: int, units, n: int, levels, tol, d_out: int, capacity: int,
+                 d_out_offsets: int, d_kept: int, d_thresh: int | None = None, d_bound: int | None = None):
+        """wc_thin_tol: standard payloads -> what wc_forward_levels_tol's rule keeps of them
+        at the per-unit RMSE tolerances tol (host doubles).  wc_forward's slot layout."""
+        lv = _levels_array(levels, n)
+        t = _tol_array(tol, n)
+        self._check(self._L.wc_thin_tol(self._h, ctypes.c_void_p(d_payload), ctypes.c_void_p(d_offsets), units, n,
+                                        lv.ctypes.data, t.ctypes.data, ctypes.c_void_p(d_out), int(capacity),
+                                        ctypes.c_void_p(d_out_offsets), ctypes.c_void_p(d_kept),
+                                        ctypes.c_void_p(d_thresh or 0), ctypes.c_void_p(d_bound or 0)))
+
+    def split_tol(self, d_payload: int, d_offsets: int, units, n: int, levels, tol, d_base: int,
+                  base_capacity: int, d_base_offsets: int, d_kept: int, d_rest: int, rest_capacity: int,
+                  d_rest_offsets: int, d_rest_pairs: int, d_thresh: int | None = None, d_bound: int | None = None):
+        """wc_split_tol: base is thin_tol's output, rest the other candidates."""
+        lv = _levels_array(levels, n)
+        t = _tol_array(tol, n)
+        self._check(self._L.wc_split_tol(self._h, ctypes.c_void_p(d_payload), ctypes.c_void_p(d_offsets), units, n,
+                                         lv.ctypes.data, t.ctypes.data, ctypes.c_void_p(d_base), int(base_capacity),
+                                         ctypes.c_void_p(d_base_offsets), ctypes.c_void_p(d_kept),
+                                         ctypes.c_void_p(d_rest), int(rest_capacity),
+                                         ctypes.c_void_p(d_rest_offsets), ctypes.c_void_p(d_rest_pairs),
+                                         ctypes.c_void_p(d_thresh or 0), ctypes.c_void_p(d_bound or 0)))
 
     def split_budget(self, d_payload: int, d_offsets: int, units, n: int, levels, max_pairs, d_base: int,
                      base_capacity: int, d_base_offsets: int, d_kept: int, d_rest: int, rest_capacity: int,
@@ -758,6 +792,45 @@ class Context:
                                                  base.ctypes.data, bcap, boff.ctypes.data, kept.ctypes.data,
                                                  rest.ctypes.data, rcap, roff.ctypes.data, rpairs.ctypes.data))
         return base, boff, kept[:n], rest, roff, rpairs[:n], None, None
+
+    def thin_tol_host(self, payload: np.ndarray, offsets: np.ndarray, units, n: int, tol, levels=None):
+        """wc_thin_tol_host -> (out, out_offsets, kept, thresh [n, WC_MAX_LEVELS], bound),
+        packed as forward_host.  levels None: from the headers."""
+        p = np.ascontiguousarray(payload, np.uint8)
+        off = np.ascontiguousarray(offsets, np.uint64)
+        lv = None if levels is None else _levels_array(levels, n)
+        t = _tol_array(tol, n)
+        cap = thin_bound(units, n, None)
+        out = np.empty(cap, np.uint8)
+        out_offsets = np.zeros(n + 1, np.uint64)
+        kept = np.zeros(max(n, 1), np.uint32)
+        th = np.zeros((max(n, 1), WC_MAX_LEVELS), np.float32)
+        bound = np.zeros(max(n, 1), np.float64)
+        self._check(self._L.wc_thin_tol_host(self._h, p.ctypes.data, off.ctypes.data, units, n,
+                                             None if lv is None else lv.ctypes.data, t.ctypes.data, out.ctypes.data,
+                                             cap, out_offsets.ctypes.data, kept.ctypes.data, th.ctypes.data,
+                                             bound.ctypes.data))
+        return out, out_offsets, kept[:n], th[:n], bound[:n]
+
+    def split_tol_host(self, payload: np.ndarray, offsets: np.ndarray, units, n: int, tol, levels=None):
+        """wc_split_tol_host -> (base, base_offsets, kept, rest, rest_offsets, rest_pairs,
+        thresh [n, WC_MAX_LEVELS], bound), both packed as forward_host."""
+        p = np.ascontiguousarray(payload, np.uint8)
+        off = np.ascontiguousarray(offsets, np.uint64)
+        lv = None if levels is None else _levels_array(levels, n)
+        t = _tol_array(tol, n)
+        bcap, rcap = split_bound(units, n, None)
+        base, rest = np.empty(bcap, np.uint8), np.empty(rcap, np.uint8)
+        boff, roff = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
+        kept, rpairs = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        th = np.zeros((max(n, 1), WC_MAX_LEVELS), np.float32)
+        bound = np.zeros(max(n, 1), np.float64)
+        self._check(self._L.wc_split_tol_host(self._h, p.ctypes.data, off.ctypes.data, units, n,
+                                              None if lv is None else lv.ctypes.data, t.ctypes.data,
+                                              base.ctypes.data, bcap, boff.ctypes.data, kept.ctypes.data,
+                                              rest.ctypes.data, rcap, roff.ctypes.data, rpairs.ctypes.data,
+                                              th.ctypes.data, bound.ctypes.data))
+        return base, boff, kept[:n], rest, roff, rpairs[:n], th[:n], bound[:n]
 
     def merge_host(self, a: np.ndarray, a_offsets: np.ndarray, b: np.ndarray, b_offsets: np.ndarray, units, n: int,
                    levels=None):
@@ -1200,6 +1273,41 @@ def thin_unit(payload, max_pairs=None, thresh=None):
     if rc != 0:
         raise WaveletError(rc, "wc_thin_unit: refused")
     return out[:written.value].tobytes(), int(key.value), tout[:payload_levels(bytes(payload[:20]))].copy()
+
+
+def thin_tol_unit(payload, tol: float, cap=None):
+    """wc_thin_tol_unit (host only): the tolerance rule on one standard payload ->
+    (bytes, fp32 thresholds of levels 1..L, bound)."""
+    p = np.frombuffer(bytes(payload), np.uint8)
+    out = np.empty(max(p.size, 20) if cap is None else max(int(cap), 1), np.uint8)
+    written = ctypes.c_size_t(0)
+    tout = np.zeros(WC_MAX_LEVELS, np.float32)
+    bound = ctypes.c_double(0.0)
+    rc = load_library().wc_thin_tol_unit(p.ctypes.data, p.size, float(tol), out.ctypes.data,
+                                         out.size if cap is None else int(cap), ctypes.byref(written),
+                                         tout.ctypes.data, ctypes.byref(bound))
+    if rc != 0:
+        raise WaveletError(rc, "wc_thin_tol_unit: refused")
+    return out[:written.value].tobytes(), tout[:payload_levels(bytes(payload[:20]))].copy(), float(bound.value)
+
+
+def split_tol_unit(payload, tol: float, base_cap=None, rest_cap=None):
+    """wc_split_tol_unit (host only): the tolerance rule on one standard payload ->
+    (base bytes, rest bytes, fp32 thresholds of levels 1..L, bound)."""
+    p = np.frombuffer(bytes(payload), np.uint8)
+    base = np.empty(max(p.size, 20) if base_cap is None else max(int(base_cap), 1), np.uint8)
+    rest = np.empty(max(p.size, 20) if rest_cap is None else max(int(rest_cap), 1), np.uint8)
+    bl, rl = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    tout = np.zeros(WC_MAX_LEVELS, np.float32)
+    bound = ctypes.c_double(0.0)
+    rc = load_library().wc_split_tol_unit(p.ctypes.data, p.size, float(tol), base.ctypes.data,
+                                          base.size if base_cap is None else int(base_cap), ctypes.byref(bl),
+                                          rest.ctypes.data, rest.size if rest_cap is None else int(rest_cap),
+                                          ctypes.byref(rl), tout.ctypes.data, ctypes.byref(bound))
+    if rc != 0:
+        raise WaveletError(rc, "wc_split_tol_unit: refused")
+    return (base[:bl.value].tobytes(), rest[:rl.value].tobytes(),
+            tout[:payload_levels(bytes(payload[:20]))].copy(), float(bound.value))
 
 
 def split_bound(units, n: int, max_pairs=None):

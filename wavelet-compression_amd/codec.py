@@ -175,13 +175,21 @@ def _standard_payloads(payloads: Sequence[bytes], device: int = 0) -> List[bytes
     return out
 
 
-def _selection(dims, n, max_bytes, ratio, thresh):
-    """thin_payloads' and split_payloads' arguments -> (pair budgets or None, n x WC_MAX_LEVELS thresholds or None)."""
-    if sum(v is not None for v in (max_bytes, ratio, thresh)) != 1:
-        raise ValueError("exactly one of max_bytes, ratio and thresh")
+def _selection(dims, n, max_bytes, ratio, thresh, rmse=None):
+    """thin_payloads' and split_payloads' arguments -> (pair budgets or None, n x WC_MAX_LEVELS thresholds or None,
+    n tolerances or None)."""
+    if sum(v is not None for v in (max_bytes, ratio, thresh, rmse)) != 1:
+        raise ValueError("exactly one of max_bytes, ratio, thresh and rmse")
     if n == 0:
-        return None, None
+        return None, None, None
     pairs = th = None
+    if rmse is not None:
+        tol = np.full(n, float(rmse), np.float64) if np.ndim(rmse) == 0 else np.asarray(rmse, np.float64)
+        if tol.shape != (n,):
+            raise ValueError(f"rmse: one value or {n} values")
+        if not (tol >= 0).all():
+            raise ValueError("rmse: tolerances >= 0 (NaN is none)")
+        return None, None, tol
     if thresh is not None:
         th = np.zeros((n, capi.WC_MAX_LEVELS), np.float32)
         if np.ndim(thresh) == 0:
@@ -205,10 +213,11 @@ def _selection(dims, n, max_bytes, ratio, thresh):
             if any(v < 20 for v in budget):
                 raise ValueError("max_bytes: a payload's header alone takes 20 bytes")
         pairs = [min((v - 20) // 8, 0xFFFFFFFF) for v in budget]
-    return pairs, th
+    return pairs, th, None
 
 
-def thin_payloads(payloads: Sequence[bytes], max_bytes=None, ratio=None, thresh=None, device: int = 0) -> List[bytes]:
+def thin_payloads(payloads: Sequence[bytes], max_bytes=None, ratio=None, thresh=None, device: int = 0,
+                  rmse=None) -> List[bytes]:
     """Payloads -> smaller payloads in the compressed domain (not in the reference;
     wc_thin_budget_host / wc_thin_thresh_host): no cell and no dense coefficient
     exists in between, and the result is what the forward's selection gives on the
@@ -217,39 +226,50 @@ def thin_payloads(payloads: Sequence[bytes], max_bytes=None, ratio=None, thresh=
     (max_bytes - 20) // 8 largest weighted coefficients and never more (ties at the
     boundary are all dropped); ratio: max_bytes = max(20, floor(4 * N / ratio)) for
     a box of N cells.  thresh (one float >= 0, or L per payload): keeps |c| > thresh
-    on every level (or thresh[i][lvl - 1]).  Exactly one of the three.  The levels
-    come from the headers.  Packed units are unpacked first; the results are
-    standard payloads."""
+    on every level (or thresh[i][lvl - 1]).  rmse (one value >= 0, or one per
+    payload; wc_thin_tol_host): the RMSE this thinning may add, with one threshold
+    per level as compress_payloads(rmse=) picks them; a payload written at rmse0
+    and thinned at rmse1 is within sqrt(rmse0^2 + rmse1^2) of the original box, and
+    a payload that holds every non-zero coefficient gives the bytes of
+    compress_payloads(rmse=).  Boxes with cells need even dimensions.  Exactly one
+    of the four.  The levels come from the headers.  Packed units are unpacked
+    first; the results are standard payloads."""
     if not payloads:
-        _selection([], 0, max_bytes, ratio, thresh)
+        _selection([], 0, max_bytes, ratio, thresh, rmse)
         return []
     std = _standard_payloads(payloads, device)
     dims = _header_dims(std)
     units, n, _ = capi.make_units(dims)
     buf, offsets = _laid_out(std)
-    pairs, th = _selection(dims, n, max_bytes, ratio, thresh)
-    out, off, kept = context(device).thin_host(buf, offsets, units, n, None, max_pairs=pairs, thresh=th)[:3]
+    pairs, th, tol = _selection(dims, n, max_bytes, ratio, thresh, rmse)
+    if tol is not None:
+        out, off, kept = context(device).thin_tol_host(buf, offsets, units, n, tol)[:3]
+    else:
+        out, off, kept = context(device).thin_host(buf, offsets, units, n, None, max_pairs=pairs, thresh=th)[:3]
     return [capi.unit_payload(out, off, kept, i) for i in range(n)]
 
 
-def split_payloads(payloads: Sequence[bytes], max_bytes=None, ratio=None, thresh=None, device: int = 0):
+def split_payloads(payloads: Sequence[bytes], max_bytes=None, ratio=None, thresh=None, device: int = 0, rmse=None):
     """Payloads -> (bases, rests) in the compressed domain (not in the reference;
-    wc_split_budget_host / wc_split_thresh_host).  bases[i] is exactly what
+    wc_split_budget_host / wc_split_thresh_host / wc_split_tol_host).  bases[i] is exactly what
     thin_payloads gives with the same arguments; rests[i] holds every other
     candidate of the payload (its non-zero, non-NaN coefficients), so that
     merge_payloads(bases, rests) is the payload again, byte for byte, for every
     payload an encoder of this project emitted.  Splitting rests[i] again yields the
     next layer.  Packed units are unpacked first; the results are standard payloads."""
     if not payloads:
-        _selection([], 0, max_bytes, ratio, thresh)
+        _selection([], 0, max_bytes, ratio, thresh, rmse)
         return [], []
     std = _standard_payloads(payloads, device)
     dims = _header_dims(std)
     units, n, _ = capi.make_units(dims)
     buf, offsets = _laid_out(std)
-    pairs, th = _selection(dims, n, max_bytes, ratio, thresh)
-    base, boff, kept, rest, roff, rpairs = context(device).split_host(buf, offsets, units, n, None, max_pairs=pairs,
-                                                                      thresh=th)[:6]
+    pairs, th, tol = _selection(dims, n, max_bytes, ratio, thresh, rmse)
+    if tol is not None:
+        base, boff, kept, rest, roff, rpairs = context(device).split_tol_host(buf, offsets, units, n, tol)[:6]
+    else:
+        base, boff, kept, rest, roff, rpairs = context(device).split_host(buf, offsets, units, n, None, max_pairs=pairs,
+                                                                          thresh=th)[:6]
     return ([capi.unit_payload(base, boff, kept, i) for i in range(n)],
             [capi.unit_payload(rest, roff, rpairs, i) for i in range(n)])
 

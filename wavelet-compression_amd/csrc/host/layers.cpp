@@ -1,8 +1,8 @@
-// layers.cpp — split_budget, split_thresh and merge of the C++ mirror
+// layers.cpp — split_budget, split_thresh, split_rmse and merge of the C++ mirror
 // (include/wavelet_amd/codec_extras.h): CompressedWavelet structs to (base, rest)
 // layers and layers back to one struct, in the compressed domain, each in one
-// wc_split_budget_host / wc_split_thresh_host / wc_merge_host call.  Not in the
-// reference.
+// wc_split_budget_host / wc_split_thresh_host / wc_split_tol_host / wc_merge_host
+// call.  Not in the reference.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -54,7 +54,8 @@ std::vector<CompressedWavelet> structs_of(const std::vector<uint8_t>& out, const
     return res;
 }
 
-Layers split(const std::vector<CompressedWavelet>& in, const double* ratio, const float* thresh) {
+Layers split(const std::vector<CompressedWavelet>& in, const double* ratio, const float* thresh,
+             const double* rmse = nullptr) {
     const int n = static_cast<int>(in.size());
     if (n == 0) return {};
     const Laid l = lay_out(in, "split");
@@ -76,6 +77,13 @@ Layers split(const std::vector<CompressedWavelet>& in, const double* ratio, cons
                                    base.data(), bcap, boff.data(), kept.data(), rest.data(), rcap, roff.data(),
                                    rpairs.data(), nullptr, nullptr),
               "GPU split");
+    } else if (rmse) {
+        const std::vector<double> tol((size_t)n, *rmse);
+        check(ctx,
+              wc_split_tol_host(ctx, l.buf.data(), l.offsets.data(), l.units.data(), n, nullptr, tol.data(), base.data(),
+                                bcap, boff.data(), kept.data(), rest.data(), rcap, roff.data(), rpairs.data(), nullptr,
+                                nullptr),
+              "GPU split");
     } else {
         const std::vector<float> th((size_t)n * WC_MAX_LEVELS, *thresh);
         check(ctx,
@@ -96,6 +104,11 @@ Layers split_budget(const std::vector<CompressedWavelet>& compressed, double rat
 Layers split_thresh(const std::vector<CompressedWavelet>& compressed, float thresh) {
     if (!(thresh >= 0.0f)) fatal("split_thresh: the threshold must be >= 0");
     return split(compressed, nullptr, &thresh);
+}
+
+Layers split_rmse(const std::vector<CompressedWavelet>& compressed, double rmse) {
+    if (!(rmse >= 0.0)) fatal("split_rmse: the tolerated RMSE must be >= 0");
+    return split(compressed, nullptr, nullptr, &rmse);
 }
 
 std::vector<CompressedWavelet> merge(const std::vector<CompressedWavelet>& a, const std::vector<CompressedWavelet>& b) {

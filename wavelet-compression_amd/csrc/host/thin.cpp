@@ -1,6 +1,6 @@
-// thin.cpp — thin_budget and thin_thresh of the C++ mirror (include/wavelet_amd/codec_extras.h):
+// thin.cpp — thin_budget, thin_thresh and thin_rmse of the C++ mirror (include/wavelet_amd/codec_extras.h):
 // CompressedWavelet structs to smaller ones in the compressed domain, in one
-// wc_thin_budget_host / wc_thin_thresh_host call.  Not in the reference.
+// wc_thin_budget_host / wc_thin_thresh_host / wc_thin_tol_host call.  Not in the reference.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -15,7 +15,8 @@ namespace wavelet_amd {
 
 namespace {
 
-std::vector<CompressedWavelet> thin(const std::vector<CompressedWavelet>& in, const double* ratio, const float* thresh) {
+std::vector<CompressedWavelet> thin(const std::vector<CompressedWavelet>& in, const double* ratio, const float* thresh,
+                                    const double* rmse = nullptr) {
     const int n = static_cast<int>(in.size());
     if (n == 0) return {};
     // the serialized structs back to back, each at an offset == 4 (mod 8)
@@ -47,6 +48,11 @@ std::vector<CompressedWavelet> thin(const std::vector<CompressedWavelet>& in, co
         check(ctx, wc_thin_budget_host(ctx, buf.data(), offsets.data(), units.data(), n, nullptr, pairs.data(), out.data(),
                                        cap, ooff.data(), kept.data(), nullptr, nullptr),
               "GPU thinning");
+    } else if (rmse) {
+        const std::vector<double> tol((size_t)n, *rmse);
+        check(ctx, wc_thin_tol_host(ctx, buf.data(), offsets.data(), units.data(), n, nullptr, tol.data(), out.data(), cap,
+                                    ooff.data(), kept.data(), nullptr, nullptr),
+              "GPU thinning");
     } else {
         const std::vector<float> th((size_t)n * WC_MAX_LEVELS, *thresh);
         check(ctx, wc_thin_thresh_host(ctx, buf.data(), offsets.data(), units.data(), n, nullptr, th.data(), out.data(),
@@ -73,6 +79,11 @@ std::vector<CompressedWavelet> thin_budget(const std::vector<CompressedWavelet>&
 std::vector<CompressedWavelet> thin_thresh(const std::vector<CompressedWavelet>& compressed, float thresh) {
     if (!(thresh >= 0.0f)) fatal("thin_thresh: the threshold must be >= 0");
     return thin(compressed, nullptr, &thresh);
+}
+
+std::vector<CompressedWavelet> thin_rmse(const std::vector<CompressedWavelet>& compressed, double rmse) {
+    if (!(rmse >= 0.0)) fatal("thin_rmse: the tolerated RMSE must be >= 0");
+    return thin(compressed, nullptr, nullptr, &rmse);
 }
 
 }  // namespace wavelet_amd

@@ -1436,10 +1436,14 @@ static ThinDesc thin_desc(const wc_unit& f, int L) {
 static int thin_or_split(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
                          const int32_t* levels, const uint32_t* max_pairs, const float* thresh, bool full_slots,
                          uint8_t* d_out, uint64_t out_capacity, uint64_t* d_out_offsets, uint32_t* d_kept,
-                         float* d_thresh, uint32_t* d_key, const SplitOut* so) {
+                         float* d_thresh, uint32_t* d_key, const SplitOut* so, const double* tol = nullptr,
+                         double* d_bound = nullptr) {
     const bool budget = max_pairs != nullptr;
     int rc;
     if ((rc = validate_levels(c, units, n, levels))) return rc;
+    // the tolerance form: what wc_forward_levels_tol refuses (an odd dimension passes validate_levels only at L = 1)
+    if (tol && (rc = validate_tol(c, units, n, tol))) return rc;
+    int maxl = 1;
     std::vector<ThinDesc> desc(n);
     uint64_t cursor = 4, rcursor = 4;
     for (int u = 0; u < n; ++u) {
@@ -1456,7 +1460,9 @@ static int thin_or_split(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_
         d.hmagic = N ? rows_magic(f.ny) : 0;
         d.K = budget ? max_pairs[u] : 0u;
         d.cap = budget && !full_slots ? (uint32_t)std::min<uint64_t>(d.K, N) : (uint32_t)N;
-        for (int l = 0; l < L && !budget; ++l) {
+        maxl = std::max(maxl, L);
+        if (tol) d.tol = tol[u];
+        for (int l = 0; l < L && !budget && !tol; ++l) {
             d.th[l] = thresh[(size_t)u * WC_MAX_LEVELS + l];
             if (!(d.th[l] >= 0.0f))
                 return fail(c, WC_ERR_INVALID,
@@ -1483,7 +1489,7 @@ static int thin_or_split(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_
     if ((rc = check_aligned(c, d_payload, "payload")) || (rc = check_aligned(c, d_offsets, "offsets", 8)) ||
         (rc = check_aligned(c, d_out, "out")) || (rc = check_aligned(c, d_out_offsets, "out_offsets", 8)) ||
         (rc = check_aligned(c, d_kept, "kept", 4)) || (rc = check_aligned(c, d_thresh, "thresh", 4)) ||
-        (rc = check_aligned(c, d_key, "key", 4)))
+        (rc = check_aligned(c, d_key, "key", 4)) || (rc = check_aligned(c, d_bound, "bound", 8)))
         return rc;
     if ((rc = set_device(c))) return rc;
     if ((rc = dense_plan(c, units, n, true))) return rc;  // every unit's pair tiles in dtiles
@@ -1497,7 +1503,7 @@ static int thin_or_split(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_
         const UnitDev& d = P.units[u];
         desc[u].dt_begin = d.dt_begin;
         tiles += d.ndt;
-        if (!budget || d.ndt <= solo) continue;
+        if (!(budget || tol) || d.ndt <= solo) continue;
         desc[u].slot = (uint32_t)split.size();
         split.push_back((uint32_t)u);
         for (uint32_t t = 0; t < d.ndt; t += chunk) items.push_back(make_uint2((uint32_t)u, t));
@@ -1507,11 +1513,11 @@ static int thin_or_split(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_
     const size_t o_items = sizeof(ThinDesc) * n, o_split = o_items + sizeof(uint2) * nitems,
                  in_bytes = o_split + 4 * nsplit;
     // wc_ctx::thin: [ticket[2][n] | keptw[n] | keyw[n] | (a split) restw[n] | status[2][tiles]] (cleared) |
-    //               state[nsplit] | thresh[n][4] | gbins[nsplit][4352] | s2[tiles * kFlatTile] |
-    //               s1[tiles * kFlatTile] | (a split) s3[tiles * kFlatTile]
+    //               state[nsplit] | thresh[n][4] | gbins[nsplit][4352, tolerance form: kThinTolBinStride] |
+    //               s2[tiles * kFlatTile] | s1[tiles * kFlatTile] | (a split) s3[tiles * kFlatTile]
     const size_t o_status = round_up((so ? 20ull : 16ull) * n, 8), clear_bytes = o_status + 16ull * tiles,
                  o_state = round_up(clear_bytes, 16), o_th = o_state + sizeof(BudgetState) * nsplit,
-                 o_bins = o_th + sizeof(float) * WC_MAX_LEVELS * n, o_s2 = o_bins + 4ull * 4352 * nsplit,
+                 o_bins = o_th + sizeof(float) * WC_MAX_LEVELS * n, o_s2 = o_bins + 4ull * (tol ? kThinTolBinStride : 4352) * nsplit,
                  o_s1 = round_up(o_s2 + 4ull * kFlatTile * tiles, 16), o_s3 = o_s1 + 8ull * kFlatTile * tiles,
                  total = o_s3 + (so ? 4ull * kFlatTile * tiles : 0);
     uint8_t* pin = nullptr;
@@ -1532,6 +1538,9 @@ static int thin_or_split(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_
     a.payload = d_payload;
     a.offsets = d_offsets;
     a.budget = budget;
+    a.tol = tol != nullptr;
+    a.maxl = maxl;
+    a.bound = d_bound;
     a.ordered = tile_order(c);
     a.ticket[0] = (uint32_t*)s;
     a.ticket[1] = (uint32_t*)s + n;
@@ -1580,6 +1589,21 @@ int split_device(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets,
                  float* d_thresh, uint32_t* d_key) {
     return thin_or_split(c, d_payload, d_offsets, units, n, levels, max_pairs, thresh, full_slots, d_base, base_capacity,
                          d_base_offsets, d_kept, d_thresh, d_key, &rest);
+}
+
+int thin_tol_device(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                    const int32_t* levels, const double* tol, uint8_t* d_out, uint64_t out_capacity,
+                    uint64_t* d_out_offsets, uint32_t* d_kept, float* d_thresh, double* d_bound) {
+    return thin_or_split(c, d_payload, d_offsets, units, n, levels, nullptr, nullptr, true, d_out, out_capacity,
+                         d_out_offsets, d_kept, d_thresh, nullptr, nullptr, tol, d_bound);
+}
+
+int split_tol_device(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                     const int32_t* levels, const double* tol, uint8_t* d_base, uint64_t base_capacity,
+                     uint64_t* d_base_offsets, uint32_t* d_kept, const SplitOut& rest, float* d_thresh,
+                     double* d_bound) {
+    return thin_or_split(c, d_payload, d_offsets, units, n, levels, nullptr, nullptr, true, d_base, base_capacity,
+                         d_base_offsets, d_kept, d_thresh, nullptr, &rest, tol, d_bound);
 }
 
 // wc_merge (wc_layers.hip).  The dense plan of the units gives the pair tiles of either input; the
@@ -1737,6 +1761,36 @@ int wc_thin_thresh(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offset
         return fail(c, WC_ERR_INVALID, "null buffer");
     return thin_device(c, d_payload, d_offsets, units, n, levels, nullptr, thresh, false, d_out, out_capacity,
                        d_out_offsets, d_kept, nullptr, nullptr);
+}
+
+// The tolerance forms of the thinning and of the split (wc_thin.hip): T from wc_forward_levels_tol's rule
+// on the pairs' bins.
+int wc_thin_tol(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                const int32_t* levels, const double* tol, uint8_t* d_out, uint64_t out_capacity,
+                uint64_t* d_out_offsets, uint32_t* d_kept, float* d_thresh, double* d_bound) {
+    if (!c) return WC_ERR_INVALID;
+    int rc;
+    if ((rc = validate_units(c, units, n))) return rc;
+    if (n == 0) return WC_OK;
+    if (!d_payload || !d_offsets || !levels || !tol || !d_out || !d_out_offsets || !d_kept)
+        return fail(c, WC_ERR_INVALID, "null buffer");
+    return thin_tol_device(c, d_payload, d_offsets, units, n, levels, tol, d_out, out_capacity, d_out_offsets, d_kept,
+                           d_thresh, d_bound);
+}
+
+int wc_split_tol(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                 const int32_t* levels, const double* tol, uint8_t* d_base, uint64_t base_capacity,
+                 uint64_t* d_base_offsets, uint32_t* d_kept, uint8_t* d_rest, uint64_t rest_capacity,
+                 uint64_t* d_rest_offsets, uint32_t* d_rest_pairs, float* d_thresh, double* d_bound) {
+    if (!c) return WC_ERR_INVALID;
+    int rc;
+    if ((rc = validate_units(c, units, n))) return rc;
+    if (n == 0) return WC_OK;
+    if (!d_payload || !d_offsets || !levels || !tol || !d_base || !d_base_offsets || !d_kept || !d_rest ||
+        !d_rest_offsets || !d_rest_pairs)
+        return fail(c, WC_ERR_INVALID, "null buffer");
+    return split_tol_device(c, d_payload, d_offsets, units, n, levels, tol, d_base, base_capacity, d_base_offsets, d_kept,
+                            SplitOut{d_rest, rest_capacity, d_rest_offsets, d_rest_pairs}, d_thresh, d_bound);
 }
 
 // The decoders over packed units (wc_packsrc.h): wc_unpack followed by

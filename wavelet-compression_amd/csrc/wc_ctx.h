@@ -43,6 +43,10 @@
 //                    (wc_split_unit, wc_merge_unit, plain C++, on wc_thin_unit), the bounds and
 //                    the _host forms of wc_split_budget / wc_split_thresh / wc_merge
 //                    (payload_serial with its second stream)
+//   wc_thintolrule.cpp / wc_thintolhost.cpp  the tolerance forms of both: the rule on one
+//                    payload (wc_thin_tol_unit, wc_split_tol_unit, plain C++, on
+//                    wc_tol_levels_threshold, wc_thin_unit and wc_split_unit) and
+//                    wc_thin_tol_host / wc_split_tol_host (payload_serial)
 //   wc_coarsehost.cpp host side of the reduced-resolution inverse: wc_coarse_units,
 //                    the argument checks and wc_inverse_coarse_host (a call of
 //                    wc_regionhost.cpp's inverse_compact_host)
@@ -441,6 +445,14 @@ int split_device(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets,
 int merge_device(wc_ctx* c, const uint8_t* d_a, const uint64_t* d_a_offsets, const uint8_t* d_b,
                  const uint64_t* d_b_offsets, const wc_unit* units, int n, const int32_t* levels, uint8_t* d_out,
                  uint64_t out_capacity, uint64_t* d_out_offsets, uint32_t* d_pairs);
+// wc_capi.cpp: wc_thin_tol / wc_split_tol after their null checks (the slots are wc_forward's: cap_u = N_u)
+int thin_tol_device(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                    const int32_t* levels, const double* tol, uint8_t* d_out, uint64_t out_capacity,
+                    uint64_t* d_out_offsets, uint32_t* d_kept, float* d_thresh, double* d_bound);
+int split_tol_device(wc_ctx* c, const uint8_t* d_payload, const uint64_t* d_offsets, const wc_unit* units, int n,
+                     const int32_t* levels, const double* tol, uint8_t* d_base, uint64_t base_capacity,
+                     uint64_t* d_base_offsets, uint32_t* d_kept, const SplitOut& rest, float* d_thresh,
+                     double* d_bound);
 
 // Bracket one launch with events when profiling is on.
 struct StageTimer {

@@ -146,13 +146,19 @@ struct ThinDesc {
     uint32_t slot;       // kLtSolo, or the unit's index among the split units (its global bins)
     uint32_t K;          // budget form: max_pairs
     uint32_t cap;        // pairs the slot holds: min(K, N), or N
-    float th[4];         // threshold form: t_1..t_L
+    union {
+        float th[4];     // threshold form: t_1..t_L
+        double tol;      // tolerance form (offset 72: 8-B aligned)
+    };
 };
 static_assert(sizeof(ThinDesc) == 88, "descriptor of 8-B members first");
+// The tolerance form's global bins of a split unit: WC_MAX_LEVELS level-major bin sets, then the NaN
+// pairs of each level.
+constexpr uint32_t kThinTolBinStride = 4 * 4096 + 4;  // (WC_MAX_LEVELS, WC_HIST_BINS: asserted in wc_thin.hip)
 
-// What launch_thin (wc_thin.hip) takes: the passes of wc_thin_budget / wc_thin_thresh and of
-// wc_split_budget / wc_split_thresh over the plan's decode tiles of the units (budget: the radix
-// select between the key pass and the compaction).  The kept pairs are the output (a split's base);
+// What launch_thin (wc_thin.hip) takes: the passes of wc_thin_budget / wc_thin_thresh / wc_thin_tol and of
+// wc_split_budget / wc_split_thresh / wc_split_tol over the plan's decode tiles of the units (budget: the
+// radix select between the key pass and the compaction; tol: the bin pass and the rule's walk there).  The kept pairs are the output (a split's base);
 // a split also gives the rest's side, which a thin call leaves null.
 struct ThinLaunch {
     const ThinDesc* desc;
@@ -186,6 +192,11 @@ struct ThinLaunch {
     uint32_t* rest_pairs;
     uint32_t* s3;                   // positions of the rest's pairs
     uint32_t* restw;                // per unit: rest pairs (zeroed)
+    // the tolerance form (wc_thin_tol / wc_split_tol): budget is false, T comes from the rule's walk over
+    // the unit's bins; gbins: nsplit x kThinTolBinStride words
+    bool tol;
+    int maxl;                       // the largest L of the call
+    double* bound;                  // the caller's d_bound or null
 };
 
 // What launch_merge (wc_layers.hip) takes, and its kernels by value: side 0 is a, side 1 is b.  The units'

@@ -1,7 +1,9 @@
 // wc_leveltol.h — device helpers shared by the kernels that read a staged
 // multi-level array per unit and per level: wc_leveltol.hip (the RMSE tolerance)
 // and wc_budget.hip (the size budget).  The level of a flat position, the
-// per-level LDS bins and the flat-tile loads.  Internal: not installed.
+// per-level LDS bins, the flat-tile loads and the tolerance rule's walk over a
+// unit's bins (lt_pick, which wc_thin.hip's tolerance form runs too).  Internal:
+// not installed.
 #pragma once
 
 #include "wc_device.h"
@@ -119,6 +121,71 @@ __device__ __forceinline__ void lt_bin_tiles(uint32_t* h, const float* __restric
             len = nlen;
         }
     }
+}
+
+__device__ __forceinline__ float lt_bin_threshold(int bstar) {
+    if (bstar <= 0) return 0.0f;
+    if (bstar >= 0xFF0) return __uint_as_float(0x7f7fffffu);  // FLT_MAX: only +-inf is kept
+    return __uint_as_float(((uint32_t)bstar << kHistShift) - 1u);
+}
+
+// The selection rule (include/wavelet_amd.h, wc_tol_levels_threshold) by one
+// full wave (lane ln): level 1's counts at h, level l >= 2's at h + off2 +
+// (l - 2) * kHistBins.  64 values of s per round, each lane the energy bounds
+// of its s at every level; the nonempty pairs are then taken in (s, l) order
+// (S is rounded after every add, so the order is part of the rule).  Separate
+// double multiplies and adds (-ffp-contract=off).  thresh: WC_MAX_LEVELS floats.
+// Returns the pair the walk stopped at, (s*, l*), uniform over the wave; x < 0:
+// it never stopped.
+__device__ __forceinline__ int2 lt_pick(const uint32_t* h, int off2, int L, uint64_t N, double tol, int ln,
+                                        float* thresh, double* bound) {
+    const double budget = (tol * tol) * (double)N;
+    double S = 0.0;
+    int sstar = -1, lstar = 0;
+    const int send = kHistBins + WC_LTOL_SHIFT * (L - 1);
+    for (int base = 0; base < send && sstar < 0; base += kWave) {
+        const int s = base + ln;
+        double term[WC_MAX_LEVELS];
+        unsigned long long m[WC_MAX_LEVELS], any = 0ull;
+        double w = 8.0;  // 8^l, exact
+#pragma unroll
+        for (int l = 0; l < WC_MAX_LEVELS; ++l, w *= 8.0) {
+            const int b = s - WC_LTOL_SHIFT * l;
+            const bool in = l < L && b >= 0 && b < kHistBins;
+            const uint32_t cnt = in ? h[(l ? off2 + (l - 1) * kHistBins : 0) + b] : 0u;
+            // every |c| of bin b is below hi: the float with bits (b + 1) << 19, +inf from the last finite bin on
+            const double hi = in && b < 0xFEF ? (double)__uint_as_float((uint32_t)(b + 1) << kHistShift)
+                                              : (double)__builtin_inff();
+            term[l] = (double)cnt * (w * (hi * hi));
+            m[l] = __ballot(cnt != 0u);
+            any |= m[l];
+        }
+        while (any && sstar < 0) {  // uniform
+            const int j = __ffsll((long long)any) - 1;
+            any &= any - 1;
+#pragma unroll
+            for (int l = 0; l < WC_MAX_LEVELS; ++l) {
+                if (sstar >= 0 || !((m[l] >> j) & 1ull)) continue;  // uniform
+                const double t = S + __shfl(term[l], j, kWave);
+                if (!(t <= budget)) {
+                    sstar = base + j;
+                    lstar = l + 1;
+                } else {
+                    S = t;
+                }
+            }
+        }
+    }
+    if (ln == 0) {
+#pragma unroll
+        for (int l = 1; l <= WC_MAX_LEVELS; ++l) {
+            int bstar = kHistBins;
+            if (sstar >= 0) bstar = min(max(sstar + (l < lstar ? 1 : 0) - WC_LTOL_SHIFT * (l - 1), 0), kHistBins);
+            thresh[l - 1] = l <= L ? lt_bin_threshold(bstar) : 0.0f;
+        }
+        if (bound) *bound = N ? sqrt(S / (double)N) : 0.0;
+    }
+    return make_int2(sstar, lstar);
 }
 
 }  // namespace wc

@@ -1,8 +1,9 @@
-// wc_thin.hip — pair selection in the compressed domain: thinning (wc_thin_budget
-// and wc_thin_thresh in include/wavelet_amd.h) and the split into progressive
-// layers (wc_split_budget and wc_split_thresh).  A payload P of a unit W x H x D
-// with L levels becomes the payload the size-budget selection, or a per-level
-// threshold test, gives on A(P), the flat array P decodes to (thinning; a split's
+// wc_thin.hip — pair selection in the compressed domain: thinning (wc_thin_budget,
+// wc_thin_thresh and wc_thin_tol in include/wavelet_amd.h) and the split into
+// progressive layers (wc_split_budget, wc_split_thresh and wc_split_tol).  A payload
+// P of a unit W x H x D with L levels becomes the payload the size-budget selection,
+// a per-level threshold test, or the RMSE-tolerance rule's thresholds give on A(P),
+// the flat array P decodes to (thinning; a split's
 // base), and, for a split, also its complement inside the canonical form of P
 // (the rest).  Thinning is a split whose rest is thrown away: one pipeline, whose
 // rest side a thin call leaves out.  No cell and no dense coefficient exists
@@ -21,7 +22,8 @@
 //                       the scratch.  Budget form: key = bg_key of a candidate at a
 //                       position below N, else 0.  Threshold form: key 2 where
 //                       |c| > t_lvl, 1 for any other candidate below N, 0 otherwise,
-//                       and T = 1 for every unit.
+//                       and T = 1 for every unit.  Tolerance form: the order key of
+//                       the rule's walk (tol_key), else 0.
 //   k_thin_solo         budget form, one workgroup per unit of up to
 //                       WC_OPT_TOL_SOLO_TILES tiles: the radix select over the unit's
 //                       keys (wc_budget.h bg_solo), then thresh[u][1..L] / key[u]
@@ -30,6 +32,14 @@
 //                       its level's offset, so a digit's counts are one plain bin
 //                       set: 4096 + 24 (L - 1) bins for the first digit, no
 //                       per-level sets and no walk over shifted sums.
+//   k_thin_tol_solo<NL>  tolerance form (wc_thin_tol / wc_split_tol), one workgroup per
+//                       unit of up to WC_OPT_TOL_SOLO_TILES tiles: the per-level LDS bins
+//                       of wc_leveltol.h filled from the scratch row's keys, the zeros
+//                       of the box added to bin 0, the rule's walk (lt_pick), then
+//                       thresh[u][1..L] / bound[u] and T = the key of the stop
+//   k_thin_tol_bins<NL> / k_thin_tol_pick   larger units: LDS bins of a run of tiles
+//                       added to the unit's 4 x 16 KiB global bins, then one wave per
+//                       unit: the zeros and the walk
 //   k_pair_compact<R>   per pair tile: kept = key > T, rest = 0 < key <= T; the
 //                       look-back is the plain sum of the counts (derive path: a
 //                       tile's own scratch row); a kept pair gets its value in the
@@ -76,12 +86,34 @@ constexpr int kThinTopBins = kHistBins + WC_LTOL_SHIFT * (WC_MAX_LEVELS - 1);  /
 constexpr int kThinBinStride = 4352;                                           // global bins per split unit
 static_assert(kThinBinStride >= kThinTopBins, "a split unit's global bins hold the first digit");
 
+// The tolerance form's order key.  The rule (include/wavelet_amd.h, wc_tol_levels_threshold) visits the
+// nonempty (s, l), s = b + WC_LTOL_SHIFT (l - 1), in lexicographic order and drops what it visits before
+// its stop (s*, l*): with code(s, l) = (s << 2) | (l - 1) a candidate is kept iff code >= code(s*, l*),
+// which is |c| > thresh_l for the thresholds the rule derives (bstar_l = s* + (l < l*) - WC_LTOL_SHIFT
+// (l - 1) is the first b of level l with code >= code(s*, l*)).  key = code + 1, so that 0 stays "no
+// candidate", and T = code(s*, l*): kept = key > T.  +-inf is above every threshold the rule can give
+// (FLT_MAX at most), yet without a stop (a budget of +inf) the walk passes its bin: it gets s = kTolInfS,
+// past every s of the walk, and T = kTolNoStop keeps exactly the +-inf pairs then.
+constexpr uint32_t kTolInfS = 0x3ffffffeu;
+constexpr uint32_t kTolNoStop = kTolInfS << 2;
+__device__ __forceinline__ uint32_t tol_key(uint32_t m, uint32_t lv) {
+    const uint32_t s = m == kBgInf ? kTolInfS : (m >> kHistShift) + (uint32_t)WC_LTOL_SHIFT * lv;
+    return ((s << 2) | lv) + 1u;
+}
+// (level index, bin) of a key
+__device__ __forceinline__ uint2 tol_unkey(uint32_t key) {
+    const uint32_t c = key - 1u, lv = c & 3u, s = c >> 2;
+    return make_uint2(lv, s == kTolInfS ? kBgInf >> kHistShift : s - (uint32_t)WC_LTOL_SHIFT * lv);
+}
+
+enum { kFormThresh = 0, kFormBudget = 1, kFormTol = 2 };
+
 // {key, pos} of every pair of the tile (a pair at or past N: key 0).  The threshold form's three
 // classes select for thinning what key = (|c| > t) would: the host refuses a threshold that is NaN
 // or negative, so t >= 0, and then float(m) > t implies 1 <= m <= 0x7F800000, which is
 // bg_candidate(m) (+-0 and NaN are not above t, and denormals are not flushed in this build): the
 // pairs with key 2 are the pairs with |c| > t, and T = 1 keeps exactly those.
-template <bool kBudget>
+template <int kForm>
 __global__ __launch_bounds__(kThreads) void k_pair_keys(const ThinDesc* __restrict__ desc,
                                                       const FTile* __restrict__ tiles,
                                                       const uint8_t* __restrict__ payload,
@@ -117,8 +149,10 @@ __global__ __launch_bounds__(kThreads) void k_pair_keys(const ThinDesc* __restri
             const uint32_t m = tp.q[r].y & 0x7fffffffu;
             const uint32_t lv = (lt_levels4(G, p & ~3u) >> (2u * (p & 3u))) & 3u;
             e.y = p;
-            if (kBudget) {
+            if (kForm == kFormBudget) {
                 e.x = bg_candidate(m) ? bg_key(m, lv) : 0u;
+            } else if (kForm == kFormTol) {
+                e.x = bg_candidate(m) ? tol_key(m, lv) : 0u;
             } else {
                 const float th = lv == 0u ? C.th[0] : lv == 1u ? C.th[1] : lv == 2u ? C.th[2] : C.th[3];
                 e.x = !bg_candidate(m) ? 0u : __uint_as_float(m) > th ? 2u : 1u;  // strict
@@ -225,6 +259,160 @@ __global__ __launch_bounds__(kWave) void k_thin_pick(const ThinDesc* __restrict_
     bg_pick<P>(
         state + blockIdx.x, L, desc[u].K, [&](int s) { return h[s]; }, h,
         [&](uint32_t T) { thin_write(T, L, u, thresh, keyw, key_out); });
+}
+
+// ---- the tolerance rule over a unit's keys (wc_leveltol.h) ----------------------------------------------
+// cnt[l][b] of A(P) from the pairs alone: a candidate counts in the bin of its key; every position of
+// level l that holds no pair, or a +-0 pair, is a zero of bin 0; a NaN pair counts nowhere.  So bin 0 of
+// level l gets N_l - (candidates of level l) - (NaN pairs of level l below N) more, N_l the positions of
+// level l in the box.
+static_assert(kThinTolBinStride == WC_MAX_LEVELS * kHistBins + WC_MAX_LEVELS, "a split unit's bin sets and NaN counts");
+
+__device__ __forceinline__ uint32_t tol_level_size(const ThinDesc& C, int l) {  // l = level - 1
+    const uint32_t a = ((uint32_t)C.W >> l) * ((uint32_t)C.H >> l) * ((uint32_t)C.D >> l);
+    const int j = l + 1;
+    return j < (int)C.L ? a - ((uint32_t)C.W >> j) * ((uint32_t)C.H >> j) * ((uint32_t)C.D >> j) : a;
+}
+
+// Pairs [k0, k1) of a scratch row into the per-level LDS bins h (lt_add1's layout) and the NaN pairs
+// below N into nan[level - 1].  A key-0 pair below N is +-0 or NaN: its value decides, its level comes
+// from its position (such pairs are rare: no encoder of this project emits one).
+__device__ __forceinline__ void tol_bin(uint32_t* h, uint32_t* nan, const ThinDesc& C, const ThinUnit& U,
+                                        const uint2* __restrict__ row, uint32_t k0, uint32_t k1) {
+    const uint32_t set = threadIdx.x & 1u;
+    for (uint32_t k = k0 + threadIdx.x; k < k1; k += kLtThreads) {
+        const uint2 e = row[k];
+        if (e.x) {
+            const uint2 lb = tol_unkey(e.x);
+            lt_add1(h, set, __uint_as_float(lb.y << kHistShift), lb.x);
+        } else if (e.y != 0xffffffffu && (U.runs[2 * (size_t)k + 1] & 0x7fffffffu) > kBgInf) {
+            const LtGeom G{C.dmagic, C.hmagic, (uint32_t)C.W, (uint32_t)C.H, (uint32_t)C.D, (int)C.L};
+            atomicAdd(nan + ((lt_levels4(G, e.y & ~3u) >> (2u * (e.y & 3u))) & 3u), 1u);
+        }
+    }
+}
+
+__device__ __forceinline__ uint32_t wave_sum32(uint32_t a) {
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) a += __shfl_xor(a, o, kWave);
+    return a;
+}
+
+// T and the outputs of unit u from the stop of the walk
+__device__ __forceinline__ void tol_write(int2 stop, uint32_t u, uint32_t* __restrict__ keyw) {
+    keyw[u] = stop.x < 0 ? kTolNoStop : ((uint32_t)stop.x << 2) | (uint32_t)(stop.y - 1);
+}
+
+// A unit whose header disagrees: no pair is read; thresholds and bound 0 (its slot stays untouched).
+__device__ __forceinline__ void tol_refused(uint32_t u, float* __restrict__ thresh, double* __restrict__ bound,
+                                            uint32_t* __restrict__ keyw) {
+#pragma unroll
+    for (int l = 0; l < WC_MAX_LEVELS; ++l) thresh[(size_t)u * WC_MAX_LEVELS + l] = 0.0f;
+    if (bound) bound[u] = 0.0;
+    keyw[u] = kTolNoStop;
+}
+
+// Workgroup u owns unit u unless the unit is split (desc[u].slot != kLtSolo).  NL = the largest L of
+// the call; LDS as k_ltol_solo<NL>: (NL + 1) x 16 KiB.
+template <int NL>
+__global__ __launch_bounds__(kLtThreads) void k_thin_tol_solo(const ThinDesc* __restrict__ desc,
+                                                            const uint8_t* __restrict__ payload,
+                                                            const uint64_t* __restrict__ offsets,
+                                                            const uint2* __restrict__ s1, float* __restrict__ thresh,
+                                                            double* __restrict__ bound, uint32_t* __restrict__ keyw) {
+    const uint32_t u = blockIdx.x;
+    const ThinDesc C = desc[u];
+    if (C.slot != kLtSolo) return;  // uniform
+    __shared__ uint32_t h[(NL + 1) * kHistBins];
+    __shared__ uint32_t cnt[2 * WC_MAX_LEVELS];  // per level: candidates, then NaN pairs
+    const ThinUnit U = thin_open(C, payload, offsets[u]);
+    if (!U.ok) {  // uniform
+        if (threadIdx.x == 0) tol_refused(u, thresh, bound, keyw);
+        return;
+    }
+    const int L = min((int)C.L, NL);  // (C.L <= NL by the caller; the bound of h all the same)
+    if (threadIdx.x < 2 * WC_MAX_LEVELS) cnt[threadIdx.x] = 0u;
+    lt_zero(h, (NL + 1) * kHistBins);
+    tol_bin(h, cnt + WC_MAX_LEVELS, C, U, s1 + (size_t)C.dt_begin * kFlatTile, 0u, U.np);
+    lt_fold(h);
+    for (int l = 0; l < L; ++l) {
+        const uint32_t* hl = h + lt_base(l + 1);
+        uint32_t a = 0u;
+        for (int i = threadIdx.x; i < kHistBins; i += kLtThreads) a += hl[i];
+        a = wave_sum32(a);
+        if ((threadIdx.x & (kWave - 1)) == 0) atomicAdd(cnt + l, a);
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < L) {
+        const int l = (int)threadIdx.x;
+        h[lt_base(l + 1)] += tol_level_size(C, l) - cnt[l] - cnt[WC_MAX_LEVELS + l];
+    }
+    __syncthreads();
+    if (threadIdx.x < kWave) {
+        const int2 stop = lt_pick(h, 2 * kHistBins, L, (uint64_t)C.N, C.tol, (int)threadIdx.x,
+                                  thresh + (size_t)u * WC_MAX_LEVELS, bound ? bound + u : nullptr);
+        if (threadIdx.x == 0) tol_write(stop, u, keyw);
+    }
+}
+
+// Work item i: pair tiles [items[i].y, + chunk) of split unit items[i].x, added to the unit's global
+// bins gbins + slot * kThinTolBinStride (zeroed by the caller).
+template <int NL>
+__global__ __launch_bounds__(kLtThreads) void k_thin_tol_bins(const ThinDesc* __restrict__ desc,
+                                                            const uint8_t* __restrict__ payload,
+                                                            const uint64_t* __restrict__ offsets,
+                                                            const uint2* __restrict__ items, uint32_t chunk,
+                                                            const uint2* __restrict__ s1,
+                                                            uint32_t* __restrict__ gbins) {
+    const uint2 it = items[blockIdx.x];
+    const ThinDesc C = desc[it.x];
+    const ThinUnit U = thin_open(C, payload, offsets[it.x]);
+    const uint32_t k0 = it.y * (uint32_t)kFlatTile;  // < 2^31: a tile of the plan
+    const uint32_t k1 = (uint32_t)min((uint64_t)U.np, (uint64_t)k0 + (uint64_t)chunk * kFlatTile);
+    if (k0 >= k1) return;  // uniform: no pair of the payload in these tiles (a refused unit: np = 0)
+    __shared__ uint32_t h[(NL + 1) * kHistBins];
+    __shared__ uint32_t nan[WC_MAX_LEVELS];
+    if (threadIdx.x < WC_MAX_LEVELS) nan[threadIdx.x] = 0u;
+    lt_zero(h, (NL + 1) * kHistBins);
+    tol_bin(h, nan, C, U, s1 + (size_t)C.dt_begin * kFlatTile, k0, k1);
+    lt_fold(h);
+    uint32_t* __restrict__ g = gbins + (size_t)C.slot * kThinTolBinStride;
+    const int L = min((int)C.L, NL);
+    for (int l = 0; l < L; ++l) {
+        const uint32_t* hl = h + lt_base(l + 1);
+        for (int i = threadIdx.x; i < kHistBins; i += kLtThreads)
+            if (hl[i]) atomicAdd(g + l * kHistBins + i, hl[i]);
+    }
+    if ((int)threadIdx.x < L && nan[threadIdx.x])
+        atomicAdd(g + WC_MAX_LEVELS * kHistBins + threadIdx.x, nan[threadIdx.x]);
+}
+
+// Workgroup s (one wave): the zeros of bin 0 and the walk of split unit split_units[s] over its global bins.
+__global__ __launch_bounds__(kWave) void k_thin_tol_pick(const ThinDesc* __restrict__ desc,
+                                                       const uint8_t* __restrict__ payload,
+                                                       const uint64_t* __restrict__ offsets,
+                                                       const uint32_t* __restrict__ split_units, uint32_t* gbins,
+                                                       float* __restrict__ thresh, double* __restrict__ bound,
+                                                       uint32_t* __restrict__ keyw) {
+    const uint32_t u = split_units[blockIdx.x];
+    const ThinDesc C = desc[u];
+    const ThinUnit U = thin_open(C, payload, offsets[u]);
+    if (!U.ok) {  // uniform
+        if (threadIdx.x == 0) tol_refused(u, thresh, bound, keyw);
+        return;
+    }
+    uint32_t* g = gbins + (size_t)blockIdx.x * kThinTolBinStride;
+    const int L = (int)C.L;
+    for (int l = 0; l < L; ++l) {
+        uint32_t a = 0u;
+        for (int i = threadIdx.x; i < kHistBins; i += kWave) a += g[l * kHistBins + i];
+        a = wave_sum32(a);
+        if (threadIdx.x == 0) g[l * kHistBins] += tol_level_size(C, l) - a - g[WC_MAX_LEVELS * kHistBins + l];
+    }
+    __syncthreads();  // (one wave: lane 0's stores before every lane's loads)
+    const int2 stop = lt_pick(g, kHistBins, L, (uint64_t)C.N, C.tol, (int)threadIdx.x, thresh + (size_t)u * WC_MAX_LEVELS,
+                              bound ? bound + u : nullptr);
+    if (threadIdx.x == 0) tol_write(stop, u, keyw);
 }
 
 // ---- compaction ---------------------------------------------------------------------------------------
@@ -376,16 +564,30 @@ __global__ __launch_bounds__(kThreads) void k_pair_units(const ThinDesc* __restr
     if (u == n - 1) rest_offsets[n] = C.rest_off + 20 + 8ull * kr;
 }
 
+// f(std::integral_constant<int, NL>), NL = the call's largest L
+template <class F>
+static void by_levels(int maxl, F f) {
+    switch (maxl) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        default: f(std::integral_constant<int, 4>{}); break;
+    }
+}
+
 hipError_t launch_thin(hipStream_t st, const ThinLaunch& a) {
     if (a.n <= 0) return hipSuccess;
     hipError_t e = hipSuccess;
     if (a.ntiles) {
         if (a.budget)
-            k_pair_keys<true><<<a.ntiles, kThreads, 0, st>>>(a.desc, a.tiles, a.payload, a.offsets, a.ticket[0],
-                                                           a.status[0], a.s1, a.err, a.ordered);
+            k_pair_keys<kFormBudget><<<a.ntiles, kThreads, 0, st>>>(a.desc, a.tiles, a.payload, a.offsets, a.ticket[0],
+                                                                  a.status[0], a.s1, a.err, a.ordered);
+        else if (a.tol)
+            k_pair_keys<kFormTol><<<a.ntiles, kThreads, 0, st>>>(a.desc, a.tiles, a.payload, a.offsets, a.ticket[0],
+                                                               a.status[0], a.s1, a.err, a.ordered);
         else
-            k_pair_keys<false><<<a.ntiles, kThreads, 0, st>>>(a.desc, a.tiles, a.payload, a.offsets, a.ticket[0],
-                                                            a.status[0], a.s1, a.err, a.ordered);
+            k_pair_keys<kFormThresh><<<a.ntiles, kThreads, 0, st>>>(a.desc, a.tiles, a.payload, a.offsets, a.ticket[0],
+                                                                  a.status[0], a.s1, a.err, a.ordered);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if (a.budget && (uint32_t)a.n > a.nsplit) {
@@ -406,7 +608,26 @@ hipError_t launch_thin(hipStream_t st, const ThinLaunch& a) {
             });
         if (e != hipSuccess) return e;
     }
-    const uint32_t* keyw = a.budget ? a.keyw : nullptr;  // threshold form: T = 1
+    if (a.tol && (uint32_t)a.n > a.nsplit) {
+        by_levels(a.maxl, [&](auto NL) {
+            k_thin_tol_solo<decltype(NL)::value><<<(uint32_t)a.n, kLtThreads, 0, st>>>(a.desc, a.payload, a.offsets, a.s1,
+                                                                                      a.thresh, a.bound, a.keyw);
+        });
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    if (a.tol && a.nsplit) {
+        if ((e = hipMemsetAsync(a.gbins, 0, sizeof(uint32_t) * kThinTolBinStride * (size_t)a.nsplit, st)) != hipSuccess)
+            return e;
+        by_levels(a.maxl, [&](auto NL) {
+            k_thin_tol_bins<decltype(NL)::value><<<a.nitems, kLtThreads, 0, st>>>(a.desc, a.payload, a.offsets, a.items,
+                                                                                 a.chunk, a.s1, a.gbins);
+        });
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        k_thin_tol_pick<<<a.nsplit, kWave, 0, st>>>(a.desc, a.payload, a.offsets, a.split_units, a.gbins, a.thresh, a.bound,
+                                                   a.keyw);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    const uint32_t* keyw = a.budget || a.tol ? a.keyw : nullptr;  // threshold form: T = 1
     if (a.ntiles) {
         if (a.rest)
             k_pair_compact<true><<<a.ntiles, kThreads, 0, st>>>(a.desc, a.tiles, a.payload, a.offsets, a.ticket[1],
