@@ -537,6 +537,92 @@ int wc_forward_levels_budget_host(wc_ctx* ctx, const void* cells, int dtype, con
                                   uint64_t payload_capacity, uint64_t* offsets, uint32_t* kept, float* thresh,
                                   uint32_t* key, double* rmse);
 
+/* Opt-in pointwise (max-abs) error bound on the multi-level transform (NOT the
+ * reference's rule): the caller states E per unit and no cell of the unit's
+ * reconstruction is further than E from the original.  An RMSE tolerance says
+ * nothing about the worst cell.  The Haar model gives only the analytic bound
+ * T <= E / (7L + 1) (a cell depends on 7 detail coefficients per level plus one
+ * low-pass value, each with weight +-1), which is 3 to 6 times below what the
+ * data allows; this mode VERIFIES candidate thresholds on the device instead,
+ * by the round trip itself.
+ *
+ * Setting.  A unit W x H x D with cells and L levels, 1 <= L <= WC_MAX_LEVELS;
+ * 2^L divides W, H and D (for L = 1: even dimensions), exactly what
+ * wc_forward_levels_tol accepts.  x = the caller's cells in the caller's dtype
+ * (fp64 cells before narrowing).  A = the final flat array of
+ * wc_forward_levels.  E = the unit's bound, a double >= 0, +inf allowed; NaN or
+ * negative: WC_ERR_INVALID naming the unit, before anything is launched.
+ *
+ * Definitions.
+ *   thr(b)  for b in 0..4095, wc_tol_threshold's threshold from a first kept
+ *           bin: 0.0f at b = 0, FLT_MAX from 0xFF0 up, else the float with bits
+ *           (b << WC_HIST_SHIFT) - 1
+ *   R_b     wc_inverse_flat_levels of A with every coefficient that is not
+ *           |c| > thr(b) replaced by +0.0f (strict: NaN is dropped); bit for
+ *           bit what wc_inverse_levels returns for the payload written at that
+ *           threshold
+ *   err(b)  the max over the cells of |(double)x - (double)R_b|, taken over the
+ *           differences that are not NaN; 0.0 if there are none.  A max does
+ *           not depend on order: the host, the device and every run give the
+ *           same bits.
+ *
+ * Search (radix 16, three passes; fixed, so that the result is defined).
+ *   lo = 0
+ *   for stride = 256, 16, 1:
+ *       j* = the largest j in 0..15 such that err(lo + i*stride) <= E for
+ *            every i in 1..j;  lo += j* * stride
+ *   b* = lo, thresh = thr(b*), err = err(b*)
+ * err <= E holds whenever b* > 0.  b* = 0 is accepted unverified: it keeps
+ * every non-zero coefficient, its err is the fp32 rounding of the round trip
+ * and may exceed a tiny E; the caller sees that in err.  err(b) is NOT monotone
+ * in b (dropped coefficients cancel: of 400 random 4x4x4 boxes of integers in
+ * -8..8 at L = 2, 380 show a decreasing step), so the leading run above is the
+ * definition and "the largest b with err(b) <= E" is not.  In L-inf every level
+ * weighs +-1, so one threshold for all levels is the natural rule.
+ *
+ * Payload.  Byte for byte what wc_forward_levels writes for that unit with the
+ * explicit threshold thr(b*).  The format does not change: every decoder,
+ * wc_pack, the thinning, split and merge read it as any payload.  A unit
+ * without cells keeps nothing, with thresh 0.0f and err 0.0.
+ *
+ *   wc_maxerr_select: host-only; the rule on one unit in plain C++ (flat: the
+ *     final array, nx * ny * nz floats, x slowest; cells: the unit's cells in
+ *     dtype, x fastest).  thresh, err and bstar are nullable.
+ *   wc_forward_levels_maxerr: wc_forward_levels with per-unit bounds in place
+ *     of keep / thresh.  levels (n int32, NULL = all 1) and maxerr (n doubles):
+ *     HOST, consumed before the call returns.  d_thresh (n floats, ONE per
+ *     unit) and d_err (n doubles): device, nullable.  Asynchronous on the
+ *     context's stream; nothing is read back between its passes (46 probes per
+ *     unit in three launches).  It leaves nothing staged.
+ *   wc_forward_levels_maxerr_host: host buffers; payloads packed as
+ *     wc_forward_host; thresh, err, rmse (n each): host, nullable; rmse = the
+ *     RMSE of each unit's round trip, taken on the device (wc_inverse_levels +
+ *     wc_rmse).  The unit runs (WC_OPT_HOST_CHUNK) go one after another.
+ *   wc_maxerr / wc_maxerr_host: the L-inf sibling of wc_rmse: per unit the max
+ *     of |(double)orig - (double)regen| over the non-NaN differences, 0.0 for a
+ *     unit without cells.  Any reconstruction, the reference mode's included.
+ * A level outside 1..WC_MAX_LEVELS, a dimension that 2^L does not divide on a
+ * unit with cells (for L = 1: an odd dimension), a NaN or negative bound or a
+ * null required buffer: WC_ERR_INVALID naming the unit, before anything is
+ * launched; outputs stay untouched.
+ *
+ * Out of scope: a CLI option, a compressed-domain (wc_thin_*) form, the
+ * global-threshold mode, and per-level thresholds. */
+int wc_maxerr_select(const float* flat, const void* cells, int dtype, int32_t nx, int32_t ny, int32_t nz, int levels,
+                     double maxerr, float* thresh, double* err, uint32_t* bstar);
+int wc_forward_levels_maxerr(wc_ctx* ctx, const void* d_cells, int dtype, const wc_unit* units, int n,
+                             const int32_t* levels, const double* maxerr, uint8_t* d_payload,
+                             uint64_t payload_capacity, uint64_t* d_offsets, uint32_t* d_kept, float* d_thresh,
+                             double* d_err);
+int wc_forward_levels_maxerr_host(wc_ctx* ctx, const void* cells, int dtype, const wc_unit* units, int n,
+                                  const int32_t* levels, const double* maxerr, uint8_t* payload,
+                                  uint64_t payload_capacity, uint64_t* offsets, uint32_t* kept, float* thresh,
+                                  double* err, double* rmse);
+int wc_maxerr(wc_ctx* ctx, const void* d_orig, int dtype, const float* d_regen, const wc_unit* units, int n,
+              double* d_err);
+int wc_maxerr_host(wc_ctx* ctx, const void* orig, int dtype, const float* regen, const wc_unit* units, int n,
+                   double* err);
+
 /* Opt-in thinning in the compressed domain (not in the reference): a standard
  * payload becomes a smaller one under a tighter pair budget or under per-level
  * thresholds, without its cells or its dense coefficients ever existing.  The
@@ -1172,13 +1258,14 @@ int wc_decompose_host(wc_ctx* ctx, const void* cells, int dtype, const wc_unit* 
 #define WC_STAGE_EMIT 1       /* K2  threshold + ordered pack (k_emit) */
 #define WC_STAGE_DECODE 2     /* K5  rle_decode */
 #define WC_STAGE_INVERSE 3    /* K6  inverse transform */
-#define WC_STAGE_RMSE 4       /* K7  */
+#define WC_STAGE_RMSE 4       /* K7; also wc_maxerr */
 #define WC_STAGE_HIST 5       /* histogram pass of generic units (wc_forward_stage with d_hist; the fast
                                  units' bins are counted inside the transform stage) */
 #define WC_STAGE_PAIRS 6      /* header check + pair counts of wc_inverse_rows with a caller row index */
 #define WC_STAGE_TOL 7        /* per-unit bins + threshold pick of the RMSE-tolerance mode (wc_forward_tol); per-level bins, pick
                                  and mask pass of wc_forward_levels_tol; radix select and mask pass of
-                                 wc_forward_levels_budget; every pass of wc_thin_budget / wc_thin_thresh, of
+                                 wc_forward_levels_budget; probe passes, pick and mask pass of
+                                 wc_forward_levels_maxerr; every pass of wc_thin_budget / wc_thin_thresh, of
                                  wc_split_budget / wc_split_thresh and of wc_merge */
 #define WC_STAGE_LEVELS 8    /* level passes, key pass and header patch of the multi-level mode (wc_forward_levels,
                                  wc_inverse_levels) */

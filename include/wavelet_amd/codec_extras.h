@@ -59,6 +59,18 @@ Box3D decompress_region(const std::string& file_path, std::array<int, 3> lo, std
 std::vector<CompressedWavelet> compress_rmse(multiBox3D& box, std::vector<int> components, int levels, double rmse,
                                              int time, int level, int box_index, std::string compressed_dir);
 
+// compress() with a pointwise error bound in place of keep (GPU,
+// wc_forward_levels_maxerr_host; not in the reference): every component of the box is
+// transformed with the levels its dimensions admit, at most `levels` (wc_levels_for),
+// under the highest threshold of the mode's search whose round trip, verified on the
+// device, leaves no cell further than `maxerr` from the original (a bound too tight for
+// fp32 keeps every non-zero coefficient).  Writes the usual per-box .xz files, which
+// decompress(), decompress_coarse() and decompress_region() read as they are, and
+// returns the structs.  A component with cells and an odd dimension, or a negative or
+// NaN bound, exits with the library's message, as the other errors do.
+std::vector<CompressedWavelet> compress_maxerr(multiBox3D& box, std::vector<int> components, int levels, double maxerr,
+                                               int time, int level, int box_index, std::string compressed_dir);
+
 // compress() under a size budget in place of keep (GPU, wc_forward_levels_budget_host;
 // not in the reference): every component of N cells is transformed with the levels
 // its dimensions admit, at most `levels`, and keeps its (max(20, floor(4 N / ratio)) -

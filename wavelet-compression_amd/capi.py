@@ -45,6 +45,7 @@ EXPORTED = (
     "wc_split_unit", "wc_merge_unit", "wc_split_bound", "wc_merge_bound", "wc_split_budget", "wc_split_thresh",
     "wc_merge", "wc_split_budget_host", "wc_split_thresh_host", "wc_merge_host",
     "wc_thin_tol_unit", "wc_split_tol_unit", "wc_thin_tol", "wc_split_tol", "wc_thin_tol_host", "wc_split_tol_host",
+    "wc_maxerr_select", "wc_forward_levels_maxerr", "wc_forward_levels_maxerr_host", "wc_maxerr", "wc_maxerr_host",
 )
 WC_MAX_LEVELS = 4  # levels of the opt-in multi-level transform (1 = the reference's codec)
 WC_PACK_MAX_CELLS = 1 << 21  # the largest unit wc_pack / wc_unpack take (the host rule has no limit)
@@ -166,6 +167,12 @@ def load_library() -> ctypes.CDLL:
                                    ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_float),
                                    ctypes.POINTER(ctypes.c_uint32)]),
         "wc_forward_levels_budget": (i32, [vp, vp, i32, up, i32, vp, vp, vp, u64, vp, vp, vp, vp]),
+        "wc_maxerr_select": (i32, [vp, vp, i32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, i32, ctypes.c_double,
+                                   vp, vp, vp]),
+        "wc_forward_levels_maxerr": (i32, [vp, vp, i32, up, i32, vp, vp, vp, u64, vp, vp, vp, vp]),
+        "wc_forward_levels_maxerr_host": (i32, [vp, vp, i32, up, i32, vp, vp, vp, u64, vp, vp, vp, vp, vp]),
+        "wc_maxerr": (i32, [vp, vp, i32, vp, up, i32, vp]),
+        "wc_maxerr_host": (i32, [vp, vp, i32, vp, up, i32, vp]),
         "wc_forward_levels_budget_host": (i32, [vp, vp, i32, up, i32, vp, vp, vp, u64, vp, vp, vp, vp, vp]),
         "wc_region_align": (i32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, i32, rp, rp]),
         "wc_region_units": (i32, [up, rp, vp, i32, up, ctypes.POINTER(u64)]),
@@ -431,6 +438,27 @@ class Context:
                                                      ctypes.c_void_p(d_payload), capacity, ctypes.c_void_p(d_offsets),
                                                      ctypes.c_void_p(d_kept), ctypes.c_void_p(d_thresh or 0),
                                                      ctypes.c_void_p(d_key or 0)))
+
+    def forward_levels_maxerr(self, d_cells: int, dtype: int, units, n: int, levels, maxerr, d_payload: int,
+                              capacity: int, d_offsets: int, d_kept: int, d_thresh: int | None = None,
+                              d_err: int | None = None):
+        """wc_forward_levels with per-unit pointwise error bounds (n host doubles, or
+        one value for all) in place of keep / thresh: no cell of a unit's
+        reconstruction is further than its bound from the original (verified on
+        the device).  levels None: all 1.  d_thresh (n floats, ONE per unit) /
+        d_err (n doubles, the achieved max error): optional device outputs."""
+        lv = None if levels is None else _levels_array(levels, n)
+        t = _tol_array(maxerr, n)
+        self._check(self._L.wc_forward_levels_maxerr(self._h, ctypes.c_void_p(d_cells), dtype, units, n,
+                                                     None if lv is None else lv.ctypes.data, t.ctypes.data,
+                                                     ctypes.c_void_p(d_payload), capacity, ctypes.c_void_p(d_offsets),
+                                                     ctypes.c_void_p(d_kept), ctypes.c_void_p(d_thresh or 0),
+                                                     ctypes.c_void_p(d_err or 0)))
+
+    def maxerr(self, d_orig: int, dtype: int, d_regen: int, units, n: int, d_err: int):
+        """wc_maxerr: per unit the max of |orig - regen| over the non-NaN differences (n device doubles)."""
+        self._check(self._L.wc_maxerr(self._h, ctypes.c_void_p(d_orig), dtype, ctypes.c_void_p(d_regen), units, n,
+                                      ctypes.c_void_p(d_err)))
 
     def thin_budget(self, d_payload: int, d_offsets: int, units, n: int, levels, max_pairs, d_out: int,
                     capacity: int, d_out_offsets: int, d_kept: int, d_thresh: int | None = None,
@@ -709,6 +737,31 @@ class Context:
                                                        kept.ctypes.data, thresh.ctypes.data, bound.ctypes.data,
                                                        rmse.ctypes.data if want_rmse else None))
         return payload, offsets, kept[:n], thresh[:n], bound[:n], rmse[:n] if want_rmse else None
+
+    def forward_levels_maxerr_host(self, cells: np.ndarray, units, n: int, levels, maxerr, want_rmse: bool = True):
+        """wc_forward_levels_maxerr_host -> (payload, offsets, kept, thresh [n], err
+        [n], rmse); err is the achieved max error of each unit, rmse the RMSE of its
+        round trip, taken on the device (None, and no round trip, without
+        want_rmse)."""
+        c = np.ascontiguousarray(cells)
+        if c.dtype not in (np.float32, np.float64):
+            raise TypeError("cells must be float32 or float64")
+        dtype = WC_F64 if c.dtype == np.float64 else WC_F32
+        lv = None if levels is None else _levels_array(levels, n)
+        t = _tol_array(maxerr, n)
+        cap = payload_bound(units, n)
+        payload = np.empty(cap, np.uint8)
+        offsets = np.zeros(n + 1, np.uint64)
+        kept = np.zeros(max(n, 1), np.uint32)
+        thresh = np.zeros(max(n, 1), np.float32)
+        err = np.zeros(max(n, 1), np.float64)
+        rmse = np.zeros(max(n, 1), np.float64) if want_rmse else None
+        self._check(self._L.wc_forward_levels_maxerr_host(self._h, c.ctypes.data, dtype, units, n,
+                                                          None if lv is None else lv.ctypes.data, t.ctypes.data,
+                                                          payload.ctypes.data, cap, offsets.ctypes.data,
+                                                          kept.ctypes.data, thresh.ctypes.data, err.ctypes.data,
+                                                          rmse.ctypes.data if want_rmse else None))
+        return payload, offsets, kept[:n], thresh[:n], err[:n], rmse[:n] if want_rmse else None
 
     def forward_levels_budget_host(self, cells: np.ndarray, units, n: int, levels, max_pairs, want_rmse: bool = True):
         """wc_forward_levels_budget_host -> (payload, offsets, kept, thresh [n,
@@ -1020,6 +1073,15 @@ class Context:
         r = np.ascontiguousarray(regen, np.float32)
         out = np.zeros(max(n, 1), np.float64)
         self._check(self._L.wc_rmse_host(self._h, o.ctypes.data, dtype, r.ctypes.data, units, n, out.ctypes.data))
+        return out[:n]
+
+    def maxerr_host(self, orig: np.ndarray, regen: np.ndarray, units, n: int) -> np.ndarray:
+        """wc_maxerr_host: per unit the max of |orig - regen| over the non-NaN differences."""
+        o = np.ascontiguousarray(orig)
+        dtype = WC_F64 if o.dtype == np.float64 else WC_F32
+        r = np.ascontiguousarray(regen, np.float32)
+        out = np.zeros(max(n, 1), np.float64)
+        self._check(self._L.wc_maxerr_host(self._h, o.ctypes.data, dtype, r.ctypes.data, units, n, out.ctypes.data))
         return out[:n]
 
     def inverse_host(self, payload: np.ndarray, offsets: np.ndarray, units, n: int, extent: int, out=None):
@@ -1383,6 +1445,26 @@ def budget_select(flat: np.ndarray, dims, levels: int, max_pairs: int):
     if rc:
         raise WaveletError(rc, "wc_budget_select: invalid argument")
     return int(key.value), [float(t[l]) for l in range(int(levels))], int(kept.value)
+
+
+def maxerr_select(flat: np.ndarray, cells: np.ndarray, dims, levels: int, maxerr: float):
+    """wc_maxerr_select (host only): (thresh, err, b*) of the max-error rule on
+    one unit: flat = its final flat array, cells = its cells (float32 or float64,
+    x fastest), dims = (W, H, D)."""
+    f = np.ascontiguousarray(flat, dtype=np.float32).ravel()
+    x = np.ascontiguousarray(cells).ravel()
+    if x.dtype not in (np.float32, np.float64):
+        raise TypeError("cells must be float32 or float64")
+    W, H, D = (int(v) for v in dims)
+    if W >= 0 and H >= 0 and D >= 0 and (f.size != W * H * D or x.size != W * H * D):
+        raise ValueError("flat and cells must have W * H * D values")
+    t, e, b = ctypes.c_float(), ctypes.c_double(), ctypes.c_uint32()
+    rc = load_library().wc_maxerr_select(f.ctypes.data, x.ctypes.data, WC_F64 if x.dtype == np.float64 else WC_F32,
+                                         W, H, D, int(levels), float(maxerr), ctypes.byref(t), ctypes.byref(e),
+                                         ctypes.byref(b))
+    if rc:
+        raise WaveletError(rc, "wc_maxerr_select: invalid argument")
+    return float(t.value), float(e.value), int(b.value)
 
 
 def unit_payload(payload: np.ndarray, offsets: np.ndarray, kept: np.ndarray, u: int) -> bytes:

@@ -296,7 +296,7 @@ def merge_payloads(a: Sequence[bytes], b: Sequence[bytes], *more: Sequence[bytes
 
 
 def compress_payloads(boxes: Sequence[np.ndarray], keep: float, device: int = 0, levels: int = 1, rmse=None,
-                      max_bytes=None, ratio=None, pack=None):
+                      max_bytes=None, ratio=None, pack=None, maxerr=None):
     """Batched forward path: list of Box3D -> list of serialized payload bytes.
 
     One wc_forward_host_units call for the whole list (all units in one launch
@@ -311,7 +311,12 @@ def compress_payloads(boxes: Sequence[np.ndarray], keep: float, device: int = 0,
     every payload is at most max_bytes long: the box keeps its (max_bytes - 20)
     // 8 largest weighted coefficients (wc_forward_levels_budget_host; ties at
     the boundary are all dropped).  ratio: max_bytes = max(20, floor(4 * N /
-    ratio)) per box of N cells.  rmse, max_bytes and ratio exclude each other.
+    ratio)) per box of N cells.  maxerr (not a reference parameter; one value or
+    one per box): no cell of a box's reconstruction is further than maxerr from
+    the box's cell, in the box's own dtype (float64 boxes are compared before
+    narrowing); the threshold is verified on the device by the round trip
+    itself (wc_forward_levels_maxerr_host); boxes with cells need even
+    dimensions.  rmse, max_bytes, ratio and maxerr exclude each other.
     The payload format is the same.  pack (not a reference parameter; None, 2,
     3 or 4): applied after any of the above, the payloads are returned as packed
     units with that many value bytes (pack_payloads); max_bytes and ratio keep
@@ -319,9 +324,10 @@ def compress_payloads(boxes: Sequence[np.ndarray], keep: float, device: int = 0,
     if pack is not None:
         if isinstance(pack, bool) or pack not in (2, 3, 4):
             raise ValueError(f"pack: None, 2, 3 or 4 value bytes, not {pack!r}")
-        return pack_payloads(compress_payloads(boxes, keep, device, levels, rmse, max_bytes, ratio), pack, device)
-    if sum(v is not None for v in (rmse, max_bytes, ratio)) > 1:
-        raise ValueError("rmse, max_bytes and ratio are mutually exclusive")
+        return pack_payloads(compress_payloads(boxes, keep, device, levels, rmse, max_bytes, ratio, maxerr=maxerr),
+                             pack, device)
+    if sum(v is not None for v in (rmse, max_bytes, ratio, maxerr)) > 1:
+        raise ValueError("rmse, max_bytes, ratio and maxerr are mutually exclusive")
     dims = [_box_dims(b) for b in boxes]
     budget = None
     if ratio is not None:
@@ -337,13 +343,18 @@ def compress_payloads(boxes: Sequence[np.ndarray], keep: float, device: int = 0,
     arrs = [np.ascontiguousarray(b, np.float32) for b in boxes]
     if not 1 <= int(levels) <= capi.WC_MAX_LEVELS:
         raise ValueError(f"levels: 1..{capi.WC_MAX_LEVELS}, not {levels!r}")
-    if levels > 1 or rmse is not None or budget is not None:
+    if levels > 1 or rmse is not None or budget is not None or maxerr is not None:
         units, n, extent = capi.make_units(dims)
-        cells = np.zeros(max(extent, 1), np.float32)
+        if maxerr is not None and any(np.asarray(b).dtype == np.float64 for b in boxes):
+            arrs = [np.ascontiguousarray(b, np.float64) for b in boxes]  # the bound holds against these cells
+        cells = np.zeros(max(extent, 1), arrs[0].dtype if arrs else np.float32)
         for i, a in enumerate(arrs):
             cells[units[i].cell_offset:units[i].cell_offset + a.size] = a.ravel()
         lv = [capi.levels_for(*d, levels) for d in dims]
-        if budget is not None:
+        if maxerr is not None:
+            payload, offsets, kept = context(device).forward_levels_maxerr_host(cells, units, n, lv, maxerr,
+                                                                                want_rmse=False)[:3]
+        elif budget is not None:
             pairs = [min((v - 20) // 8, 0xFFFFFFFF) for v in budget]
             payload, offsets, kept = context(device).forward_levels_budget_host(cells, units, n, lv, pairs,
                                                                                 want_rmse=False)[:3]

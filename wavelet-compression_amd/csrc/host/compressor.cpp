@@ -223,6 +223,40 @@ std::vector<CompressedWavelet> wavelet_amd::compress_rmse(multiBox3D& box, std::
     return write_components(payload.get(), offsets, kept, components, time, level, box_index, compressed_dir);
 }
 
+std::vector<CompressedWavelet> wavelet_amd::compress_maxerr(multiBox3D& box, std::vector<int> components, int levels,
+                                                            double maxerr, int time, int level, int box_index,
+                                                            std::string compressed_dir) {
+    const int n = static_cast<int>(components.size());
+    if (n == 0) return {};
+    if (levels < 1 || levels > WC_MAX_LEVELS)
+        fatal("compress_maxerr: levels " + std::to_string(levels) + " outside 1.." + std::to_string(WC_MAX_LEVELS));
+    // the host form takes one cell buffer: the components back to back, each start 4-element aligned
+    std::vector<wc_unit> units(n);
+    std::vector<int32_t> lv(n);
+    std::vector<double> bound(n, maxerr);
+    uint64_t extent = 0;
+    for (int c = 0; c < n; ++c) {
+        const Box3D& b = box.at(c);
+        extent = (extent + 3) / 4 * 4;
+        units[c] = wc_unit{extent, (int32_t)b.width(), (int32_t)b.height(), (int32_t)b.depth(), 0};
+        lv[c] = wc_levels_for(units[c].nx, units[c].ny, units[c].nz, levels);
+        extent += b.data_size();
+    }
+    std::vector<float> cells(extent);
+    for (int c = 0; c < n; ++c)
+        if (box.at(c).data_size())
+            std::memcpy(cells.data() + units[c].cell_offset, box.at(c).data(), sizeof(float) * box.at(c).data_size());
+    const uint64_t cap = wc_payload_bound(units.data(), n);
+    std::unique_ptr<uint8_t[]> payload(new uint8_t[cap]);
+    std::vector<uint64_t> offsets(n + 1);
+    std::vector<uint32_t> kept(n);
+    wc_ctx* ctx = thread_ctx();
+    check(ctx, wc_forward_levels_maxerr_host(ctx, cells.data(), WC_F32, units.data(), n, lv.data(), bound.data(),
+                                             payload.get(), cap, offsets.data(), kept.data(), nullptr, nullptr, nullptr),
+          "GPU forward");
+    return write_components(payload.get(), offsets, kept, components, time, level, box_index, compressed_dir);
+}
+
 std::vector<CompressedWavelet> wavelet_amd::compress_budget(multiBox3D& box, std::vector<int> components, int levels,
                                                             double ratio, int time, int level, int box_index,
                                                             std::string compressed_dir) {

@@ -10,7 +10,8 @@
 // the host-only wc_tol_threshold: wc_tolhost.cpp; wc_forward_levels_tol_host:
 // wc_leveltolhost.cpp; the host-only wc_tol_levels_threshold: wc_leveltolrule.cpp;
 // wc_forward_levels_budget_host: wc_budgethost.cpp; the host-only wc_budget_select
-// and wc_budget_thresholds: wc_budgetrule.cpp; wc_pack, wc_unpack and their _host
+// and wc_budget_thresholds: wc_budgetrule.cpp; wc_forward_levels_maxerr_host and
+// wc_maxerr_host: wc_maxerrhost.cpp; the host-only wc_maxerr_select: wc_maxerrrule.cpp; wc_pack, wc_unpack and their _host
 // forms: wc_packhost.cpp; the packed format's host-only rule: wc_packrule.cpp;
 // the packed decoders' _host forms: wc_packdecodehost.cpp;
 // wc_forward_levels_host and wc_inverse_levels_host: wc_levelshost.cpp; the
@@ -392,6 +393,28 @@ int stage_budget(wc_ctx* c, int n, int maxl, const LevelTolWork& t, const uint8_
         e = launch_leveltol_mask(c->stream, du, lt, (const FTile*)P.d_ftiles.p, (uint32_t)P.ftiles.size(),
                                  (float*)c->coef.p, th);
     return e == hipSuccess ? WC_OK : hip_fail(c, e, "size budget launch");
+}
+
+// Max-error mode, between the level passes and the emit: the three probe passes
+// and the pick of every unit (wc_maxerr.hip), then the mask pass of the
+// tolerance mode with the one threshold per unit in its slots.  The tail of the
+// blob: state[3][n][16] (zeroed) | prefix[n + 1], the units' first probe tiles.
+constexpr size_t kMaxerrStateUnit = 3 * 16 * sizeof(uint64_t);
+int stage_maxerr(wc_ctx* c, int n, int maxl, const LevelTolWork& t, const uint8_t* d_blob, const void* d_cells,
+                 int dtype, uint32_t ntiles, float* d_thresh, double* d_err) {
+    const Plan& P = c->plan;
+    float* slots = (float*)const_cast<uint8_t*>(d_blob + t.o_thresh);
+    const UnitDev* du = (const UnitDev*)P.d_units.p;
+    const LtUnit* lt = (const LtUnit*)d_blob;
+    unsigned long long* state = (unsigned long long*)const_cast<uint8_t*>(d_blob + t.o_tail);
+    const uint32_t* prefix = (const uint32_t*)(d_blob + t.o_tail + kMaxerrStateUnit * n);
+    StageTimer timer(c, WC_STAGE_TOL);
+    hipError_t e = launch_maxerr_select(c->stream, du, n, lt, prefix, ntiles, maxl, d_cells, dtype,
+                                        (const float*)c->coef.p, state, slots, d_thresh, d_err);
+    if (e == hipSuccess)
+        e = launch_leveltol_mask(c->stream, du, lt, (const FTile*)P.d_ftiles.p, (uint32_t)P.ftiles.size(),
+                                 (float*)c->coef.p, slots);
+    return e == hipSuccess ? WC_OK : hip_fail(c, e, "max-error launch");
 }
 
 bool single_level(const int32_t* levels, int n) {
@@ -1216,6 +1239,46 @@ int wc_forward_levels_budget(wc_ctx* c, const void* d_cells, int dtype, const wc
     return patch_level_headers(c, w, d_payload);
 }
 
+// Multi-level forward under a pointwise error bound per unit: wc_forward_levels'
+// staging and level passes, the probe passes, the pick and the mask pass on the
+// final array, the unchanged emit with threshold 0.0f, the header patch.  No
+// device-to-host read anywhere: the search's state stays on the device.  Leaves
+// nothing staged.
+int wc_forward_levels_maxerr(wc_ctx* c, const void* d_cells, int dtype, const wc_unit* units, int n,
+                             const int32_t* levels, const double* maxerr, uint8_t* d_payload, uint64_t cap,
+                             uint64_t* d_offsets, uint32_t* d_kept, float* d_thresh, double* d_err) {
+    std::vector<int32_t> ones;
+    bool run;
+    int rc = forward_levels_begin(
+        c, d_cells, dtype, units, n, d_payload, cap, d_offsets, d_kept, maxerr != nullptr,
+        [&] {
+            levels = levels_or_ones(levels, n, ones);
+            return validate_maxerr(c, units, n, levels, maxerr);
+        },
+        {{d_thresh, "thresh", 4}, {d_err, "err", 8}}, &run);
+    if (!run) return rc;
+    LevelWork w;
+    LevelTolWork t;
+    // the mask pass's slots are always the call's own: d_thresh holds one float per unit
+    build_leveltol(c, n, levels, maxerr, true, &t, kMaxerrStateUnit + 2 * sizeof(uint32_t));
+    int maxl = 1;
+    for (int u = 0; u < n; ++u) maxl = std::max(maxl, (int)levels[u]);
+    std::vector<uint32_t> prefix(n + 1, 0u);
+    for (int u = 0; u < n; ++u) {
+        const UnitDev& d = c->plan.units[u];
+        prefix[u + 1] = prefix[u] + (d.ncells ? maxerr_tiles(maxl, d.nx, d.ny, d.nz) : 0u);
+    }
+    std::memcpy(t.blob.data() + t.o_tail + kMaxerrStateUnit * n, prefix.data(), sizeof(uint32_t) * (n + 1));
+    const void* d_blob = nullptr;
+    const float zero = 0.0f;  // the mask pass has applied the thresholds: the emit keeps every non-zero
+    if ((rc = upload_levels(c, n, levels, &w, t.blob.data(), t.blob.size(), &d_blob)) ||
+        (rc = stage_transform(c, d_cells, dtype, 0.0, false)) || (rc = run_levels(c, w, true, false)) ||
+        (rc = stage_maxerr(c, n, maxl, t, (const uint8_t*)d_blob, d_cells, dtype, prefix[n], d_thresh, d_err)) ||
+        (rc = stage_emit(c, n, 0.0, &zero, d_payload, d_offsets, d_kept)))
+        return rc;
+    return patch_level_headers(c, w, d_payload);
+}
+
 int wc_decompose_levels(wc_ctx* c, const void* d_cells, int dtype, const wc_unit* units, int n, const int32_t* levels,
                         float* d_flat) {
     if (!c) return WC_ERR_INVALID;
@@ -1838,6 +1901,27 @@ int wc_rmse(wc_ctx* c, const void* d_orig, int dtype, const float* d_regen, cons
     hipError_t e = launch_rmse(c->stream, d_orig, dtype, d_regen, (const UnitDev*)P.d_units.p, n,
                                (const FTile*)P.d_ftiles.p, (uint32_t)P.ftiles.size(), (double*)c->part.p, d_rmse);
     return e == hipSuccess ? WC_OK : hip_fail(c, e, "rmse launch");
+}
+
+int wc_maxerr(wc_ctx* c, const void* d_orig, int dtype, const float* d_regen, const wc_unit* units, int n,
+              double* d_err) {
+    if (!c) return WC_ERR_INVALID;
+    int rc;
+    if ((rc = validate_units(c, units, n))) return rc;
+    if (dtype != WC_F32 && dtype != WC_F64) return fail(c, WC_ERR_INVALID, "dtype");
+    if (n == 0) return WC_OK;
+    if (!d_orig || !d_regen || !d_err) return fail(c, WC_ERR_INVALID, "null buffer");
+    if ((rc = check_aligned(c, d_orig, "orig", dtype == WC_F64 ? 8 : 4)) ||
+        (rc = check_aligned(c, d_regen, "regen", 4)) || (rc = check_aligned(c, d_err, "err", 8)))
+        return rc;
+    if ((rc = set_device(c)) || (rc = get_plan(c, units, n))) return rc;
+    Plan& P = c->plan;
+    hipError_t e = hipMemsetAsync(d_err, 0, sizeof(double) * n, c->stream);  // the atomic max starts from +0.0
+    if (e != hipSuccess) return hip_fail(c, e, "memset err");
+    StageTimer t(c, WC_STAGE_RMSE);
+    e = launch_maxerr(c->stream, d_orig, dtype, d_regen, (const UnitDev*)P.d_units.p, (const FTile*)P.d_ftiles.p,
+                      (uint32_t)P.ftiles.size(), d_err);
+    return e == hipSuccess ? WC_OK : hip_fail(c, e, "maxerr launch");
 }
 
 int wc_profile_enable(wc_ctx* c, int on) {

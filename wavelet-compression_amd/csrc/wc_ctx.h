@@ -32,6 +32,10 @@
 //                    selection rule on one unit's final array (plain C++, linked
 //                    alone by tests/cpp/test_budget.cpp), the argument checks
 //                    and wc_forward_levels_budget_host
+//   wc_maxerrrule.cpp / wc_maxerrhost.cpp  the pointwise (max-abs) error bound: the
+//                    search on one unit by full masked inverses (plain C++, linked
+//                    alone by tests/cpp/test_maxerr.cpp), the argument checks,
+//                    wc_forward_levels_maxerr_host and wc_maxerr_host
 //   wc_packrule.cpp / wc_packhost.cpp  packed payloads: the format's host rule
 //                    (plain C++, linked alone with wc_packfmt.h by
 //                    tests/cpp/test_pack.cpp), and wc_pack, wc_unpack and their
@@ -131,6 +135,14 @@ hipError_t launch_leveltol_mask(hipStream_t, const UnitDev*, const LtUnit*, cons
 hipError_t launch_budget(hipStream_t, const UnitDev*, int, const LtUnit*, const uint32_t* max_pairs, const uint2* items,
                          uint32_t nitems, uint32_t chunk, const uint32_t* split_units, uint32_t nsplit, int maxl,
                          const float* coef, uint32_t* gbins, BudgetState* state, float* thresh, uint32_t* key);
+// wc_maxerr.hip: the three probe passes and the pick of the max-error mode (thresh per unit into the mask pass's
+// slots; launch_leveltol_mask then applies them), the probe tiles of a unit, and the max-abs metric
+hipError_t launch_maxerr_select(hipStream_t, const UnitDev*, int, const LtUnit*, const uint32_t* prefix, uint32_t ntiles,
+                                int maxl, const void* cells, int dtype, const float* coef, unsigned long long* state,
+                                float* slots, float* thresh, double* err);
+uint32_t maxerr_tiles(int maxl, int32_t nx, int32_t ny, int32_t nz);
+hipError_t launch_maxerr(hipStream_t, const void* orig, int dtype, const float* regen, const UnitDev*, const FTile*,
+                         uint32_t, double* err);
 // wc_region.hip: the decode of the reduced-resolution and the sub-box inverse
 // (over a prefix of the full plan's decode tiles) into the compact units (whole:
 // every region is its whole primed box, wc_inverse_coarse), and the copy of the
@@ -404,6 +416,9 @@ struct SerialOut {
 // unit u's bytes are [offsets[u], end[u]); runs are split by the cells of units
 int payload_serial(wc_ctx* c, const uint8_t* bytes, const uint64_t* offsets, const uint64_t* end, const wc_unit* units,
                    int n, const PayloadStep& step, const SerialOut& o);
+
+// wc_maxerrhost.cpp: a bound per unit, each >= 0 (not NaN), and the units wc_forward_levels_tol accepts
+int validate_maxerr(wc_ctx* c, const wc_unit* units, int n, const int32_t* levels, const double* maxerr);
 
 // wc_budgethost.cpp
 int validate_budget(wc_ctx* c, const wc_unit* units, int n, const int32_t* levels);

@@ -64,33 +64,6 @@ __device__ __forceinline__ void haar8_fwd(const float (&v)[2][2][2], float (&c)[
         }
 }
 
-// Synthesis of one block, c[sx][sy][sz] -> v[dx][dy][dz]: X, then Y, then Z, as
-// k_inverse (src/decompressor.cpp:89-156).
-__device__ __forceinline__ void haar8_inv(const float (&c)[2][2][2], float (&v)[2][2][2]) {
-    float X[2][2][2], Y[2][2][2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            X[0][t][s] = c[0][t][s] + c[1][t][s];
-            X[1][t][s] = c[0][t][s] - c[1][t][s];
-        }
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            Y[x][0][s] = X[x][0][s] + X[x][1][s];
-            Y[x][1][s] = X[x][0][s] - X[x][1][s];
-        }
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int y = 0; y < 2; ++y) {
-            v[x][y][0] = Y[x][y][0] + Y[x][y][1];
-            v[x][y][1] = Y[x][y][0] - Y[x][y][1];
-        }
-}
-
 // The sub-box of a unit at one level and this workgroup's run of its blocks.
 struct LvBox {
     int H, D;        // the unit's flat strides
