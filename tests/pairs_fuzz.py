@@ -1,8 +1,10 @@
 """Seeded random batches for the pair pipeline (wc_thin_*, wc_split_*, wc_merge).
 TEST INFRASTRUCTURE ONLY: shared by tests/test_pairs_scale_cpu.py, which runs the
 batches through the host rule, and tests/test_gpu_pairs_fuzz.py, which runs them
-on the device.  Every expected result is the numpy restatement's (thin_rule.py,
-layers_rule.py), computed here once per seed.
+on the device; tol_batch() adds a tolerance per unit for tests/test_rule_fuzz_cpu.py
+and tests/test_gpu_pairs_tol_fuzz.py.  Every expected result is the numpy
+restatement's (thin_rule.py, layers_rule.py, thin_tol_rule.py), computed here once
+per seed.
 
 A batch: about 24 units of at most 2^15 cells (the 2-adic shapes of modes_batches,
 odd boxes at L = 1, a box without cells) and one of 65-70 pair tiles; L from what
@@ -159,3 +161,35 @@ def batch(seed):
     B.levels = [u.L for u in B.us]
     _memo[seed] = B
     return B
+
+
+def tol_batch(seed):
+    """The units of batch(seed) that wc_thin_tol / wc_split_tol take (thin_tol_rule.accepted), each with a
+    tolerance from a default_rng(9400 + seed) of its own, so that batch(seed) stays as it was: a kind in 0..5; 0
+    gives 0.0, 1 gives +inf, otherwise 10^U(-3, 0.5) x thin_tol_rule.weighted_rms(payload).  Every unit of
+    batch(seed) gets the fields tol, thin_tol = thin_tol_rule.thin_tol(payload, tol) and split_tol =
+    thin_tol_rule.split_tol(payload, tol); None on the refused ones.  -> us, n, dims, levels, tol, want, split."""
+    import thin_tol_rule as TT
+    if ("tol", seed) in _memo:
+        return _memo[("tol", seed)]
+    rng = np.random.default_rng(9400 + seed)
+
+    class T:
+        pass
+
+    T.seed, T.us = seed, []
+    for u in batch(seed).us:
+        u.tol = u.thin_tol = u.split_tol = None
+        if not TT.accepted(*u.dims, u.L):
+            continue
+        k, ex = int(rng.integers(0, 6)), float(rng.uniform(-3.0, 0.5))
+        u.tol = 0.0 if k == 0 else float(np.inf) if k == 1 else 10.0 ** ex * TT.weighted_rms(u.payload)
+        u.thin_tol = TT.thin_tol(u.payload, u.tol)
+        u.split_tol = TT.split_tol(u.payload, u.tol)
+        T.us.append(u)
+    T.n = len(T.us)
+    T.dims, T.levels = [u.dims for u in T.us], [u.L for u in T.us]
+    T.tol = np.array([u.tol for u in T.us], np.float64)
+    T.want, T.split = [u.thin_tol for u in T.us], [u.split_tol for u in T.us]
+    _memo[("tol", seed)] = T
+    return T
